@@ -2,7 +2,7 @@
 """bench.py -- trace steps/sec proved on the synthetic RV64I ADD/XOR loop at a 2^20 trace (BASELINE config 3).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--nv 20] [--mode traces|shard]
-                    [--no-cpu-baseline] [--kernels]
+                    [--no-cpu-baseline] [--kernels] [--dump-outputs DIR]
 
 A "step" is ONE full pass of the prover hot path over one batch of `--batch` independent 2^20-step traces (default: 8.8 per
 sponge-server thread -- 8 slots each and a tenth more proofs than slots --, 10 servers on a 16-CPU share of the host;
@@ -42,6 +42,7 @@ import os
 import socket
 import subprocess
 import sys
+import threading
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -295,6 +296,44 @@ def lasso_leg(ctx, reps=5):
     return out
 
 
+# ------------------------------------------------------------------ --dump-outputs
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_BYTES = 1 << 16  # per lane: a 2^20 proof is ~25 MB, far more than the dump may hold for 100+ lanes
+
+
+def sample_positions(n, size=DUMP_SAMPLE_BYTES):
+    """The byte offsets sampled from a proof of n bytes: all of them if n <= size, else `size` offsets drawn with a fixed seed
+    (a function of n alone), ascending."""
+    import numpy as np
+    if n <= size:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(0x5EED).integers(0, n, size))
+
+
+def dump_outputs(path, proofs, prefix="", limit=DUMP_LIMIT_BYTES):
+    """The serialised proofs of the timed region's last step (uint8 arrays, one per lane, in lane order) as float32 / float64
+    arrays under path, all values exact:
+        <prefix>proof_sha256.npy       [lanes, 32]  the SHA-256 of every lane's whole proof, one element per digest byte
+        <prefix>proof_length.npy       [lanes]      its length in bytes
+        <prefix>proof_lane<k>.npy      [<= 2^16]    lane k's bytes at sample_positions(length)
+    Lane k proves the same trace whatever the lane count, so the files of two runs pair up by name.  Sampled lanes are written
+    in order while the total stays within `limit` bytes; returns the number of lanes sampled."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    digests = np.array([list(hashlib.sha256(p).digest()) for p in proofs], dtype=np.float32).reshape(len(proofs), 32)
+    lengths = np.array([len(p) for p in proofs], dtype=np.float64)
+    np.save(os.path.join(path, prefix + "proof_sha256.npy"), digests)
+    np.save(os.path.join(path, prefix + "proof_length.npy"), lengths)
+    total = digests.nbytes + lengths.nbytes
+    for k, p in enumerate(proofs):
+        a = p[sample_positions(len(p))].astype(np.float32)
+        if total + a.nbytes > limit:
+            return k
+        np.save(os.path.join(path, "%sproof_lane%03d.npy" % (prefix, k)), a)
+        total += a.nbytes
+    return len(proofs)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -357,7 +396,14 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the single-proof, PCIe-inclusive and per-kernel legs")
     ap.add_argument("--dry-run", action="store_true", help="launcher rehearsal without a GPU: the ranks rendezvous over gloo, "
                     "all-reduce a token and rank 0 prints {dry_run, n_gpus}; nothing is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed region, write the proof every lane produced in the "
+                    "last timed step to DIR (see dump_outputs): the same arguments prove the same traces, so two builds can be "
+                    "compared proof for proof")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.kernels or args.lasso or args.dry_run):
+        ap.error("--dump-outputs writes the proofs of the timed region: not with --kernels, --lasso or --dry-run")
 
     if args.cpu_baseline_child:
         print(json.dumps(cpu_baseline_child(args.nv, args.cpu_sample_cols)))
@@ -730,10 +776,12 @@ def main():
         ls = lanes if which is None else which
         return gather([pool.submit(fn, l) for l in ls])
 
-    def timed(steps, fn=Lane.prove, which=None):
+    def timed(steps, fn=Lane.prove, which=None, keep_proofs=False):
         """Exactly `steps` steps (= steps x len(lanes) proofs) between barrier + synchronize brackets.  Every lane proves its
         `steps` traces back to back on its own host thread + HIP stream -- a proving service does not run its lanes in
-        lockstep -- and the region ends when the last lane has finished.  Returns (seconds, accumulated stats, phases)."""
+        lockstep -- and the region ends when the last lane has finished.  Returns (seconds, accumulated stats, phases).
+        keep_proofs: every lane records the thread its last proof ran on (l.proof_thread): a borrowed proof lives in a buffer of
+        that thread until the thread's next proof, so it can be read after the region without a copy inside it."""
         ls = lanes if which is None else which
         acc = {}
         acc_t = {}  # the same sums over the lanes that run in timing mode only
@@ -756,10 +804,15 @@ def main():
             for _ in range(steps):
                 out.append(fn(l))
             return out
+
+        def lane_loop_keep(l):
+            res = lane_loop(l)
+            l.proof_thread = threading.get_ident()
+            return res
         sync_all()
         c0 = time.process_time()
         t0 = time.perf_counter()
-        for l, res in zip(ls, gather([pool.submit(lane_loop, l) for l in ls])):
+        for l, res in zip(ls, gather([pool.submit(lane_loop_keep if keep_proofs else lane_loop, l) for l in ls])):
             for st, ph in res:
                 for k, v in st.items():
                     acc[k] = acc.get(k, 0) + v
@@ -794,7 +847,7 @@ def main():
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import thread_cpu
         snap0 = thread_cpu.snapshot()
-    dt, acc, phases = timed(args.steps, main_fn)  # ---- THE timed region
+    dt, acc, phases = timed(args.steps, main_fn, keep_proofs=bool(args.dump_outputs))  # ---- THE timed region
     if os.environ.get("ZIGZ_BENCH_THREAD_CPU"):
         rows, by = thread_cpu.diff(snap0, thread_cpu.snapshot())
         sys.stderr.write("thread CPU over the timed region (%.2f s wall):\n" % dt)
@@ -808,6 +861,12 @@ def main():
             except OSError:
                 wchan = "?"
             sys.stderr.write("    tid %d: user %.2f s  sys %.2f s  wchan %s\n" % (r[2], r[3], r[4], wchan))
+    if args.dump_outputs:  # (before any other proof: the lanes' borrowed proofs are still those of the last timed step)
+        if len({l.proof_thread for l in lanes}) != len(lanes):
+            raise SystemExit("bench.py: two lanes proved on one thread in the timed region; their proofs cannot be dumped")
+        import numpy as np
+        dump_outputs(args.dump_outputs, [np.ctypeslib.as_array(l.proof.ptr, (len(l.proof),)) for l in lanes],
+                     "rank%d_" % rank if world > 1 else "", DUMP_LIMIT_BYTES // world)
     nproofs = args.steps * B
     local_steps = float(sum(l.trace.num_steps for l in lanes))
     trace_steps, trace_lookups, prog = lanes[0].trace.num_steps, lanes[0].trace.num_lookups, lanes[0].prog
