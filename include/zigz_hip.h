@@ -412,6 +412,56 @@ zigz_status zigz_sumcheck_radix_run_reduced(const zigz_radix_ops *ops, size_t n_
                                             zigz_allgather_fn allgather, void *comm_user, const uint64_t *fixed_challenges,
                                             uint64_t *rounds, uint64_t *point, uint64_t *final_eval);
 
+/* ---------------------------------------------------------------- batched provers: many independent tables per call
+ * k independent SumcheckProver.prove calls (src/proofs/sumcheck_prover.zig:26-91) in shared launches: every radix pass
+ * (block sums, fold) serves all tables still in play in ONE launch, and every table keeps its own fresh transcript
+ * (src/proofs/sumcheck_protocol.zig:161).  Results are byte-identical to calling the single entry once per table, in
+ * order.  Table i has ns[i] = 2^v_i elements.  Outputs are concatenated in table order: rounds (2*v_i per table), points
+ * (v_i per table), final_evals[k].  fixed_challenges == NULL gives Fiat-Shamir; otherwise it holds sum(v_i) challenges
+ * concatenated the same way (proveInteractive, sumcheck_prover.zig:97-144).
+ * k <= ZIGZ_BATCH_MAX, else ZIGZ_ERR_INVALID_ARGUMENT; k == 0 returns ZIGZ_OK and touches nothing.  d_tables[i] must be
+ * 16-byte aligned (ZIGZ_ERR_INVALID_ARGUMENT otherwise); the same table may appear more than once.  The arguments are
+ * checked for every table before anything runs: on the first table (in index order) that the single entry would reject,
+ * the call returns that same status, writes the table's index to *bad_index (if non-NULL) and launches nothing.
+ * The batch always takes the radix schedule; the "per_round_sumcheck" option and timing mode do not apply to it. */
+#define ZIGZ_BATCH_MAX 4096
+zigz_status zigz_dev_sumcheck_prove_batch(zigz_ctx *ctx, const uint32_t *const *d_tables, const size_t *ns, size_t k,
+                                          const uint64_t *fixed_challenges, uint64_t *rounds, uint64_t *points,
+                                          uint64_t *final_evals, size_t *bad_index);
+/* host buffers (canonical u64, checked as zigz_sumcheck_prove checks them), uploaded in one copy */
+zigz_status zigz_sumcheck_prove_batch(zigz_ctx *ctx, const uint64_t *const *tables, const size_t *ns, size_t k,
+                                      const uint64_t *fixed_challenges, uint64_t *rounds, uint64_t *points,
+                                      uint64_t *final_evals, size_t *bad_index);
+/* k LassoProver.prove / proveWithMapping calls (src/lookups/lasso_prover.zig:103-205): one upload of all rows, one
+ * fingerprint launch over every table and query set, the query fingerprints proved in place by the batched sumcheck, and the
+ * 2k flat commitments (:242-252) absorbed in lock step on the host underneath it.  Instance i is given by entry i of each
+ * array, with the meaning of zigz_lasso_prove's arguments; mappings == NULL or mappings[i] == NULL: prove(), otherwise
+ * proveWithMapping() with n_mappings[i] entries.  Outputs: nv_out[i], rounds[i] (2 * nv words, caller-allocated for
+ * log2(ceilPow2(n_queries[i])) variables), points[i] (nv words), final_evals[i], and 32 bytes per instance at
+ * query_commitments + 32 i / table_commitments + 32 i.  Errors: the status the single call would return for the first failing
+ * instance, whose index goes to *bad_index (if non-NULL).  (Parallel arrays rather than a struct per instance: the binding
+ * keeps the value structs it has.) */
+zigz_status zigz_lasso_prove_batch(zigz_ctx *ctx, size_t k, const uint64_t *const *tables, const size_t *table_rows,
+                                   const uint64_t *const *queries, const size_t *n_queries, const size_t *n_in,
+                                   const size_t *n_out, const uint64_t *const *mappings, const size_t *n_mappings,
+                                   size_t *nv_out, uint64_t *const *rounds, uint64_t *const *points, uint64_t *final_evals,
+                                   uint8_t *query_commitments, uint8_t *table_commitments, size_t *bad_index);
+/* The batched orchestration over caller-supplied data passes (the batched sibling of zigz_sumcheck_radix_run).  Each
+ * callback serves `count` tables at once -- tables[j] is the index (into ns) of the j-th -- with inputs and outputs packed
+ * in that order: block_sums writes the 2^k[j] exact u64 block sums of each current table; fold folds each current table
+ * with its 2^k[j] canonical weights (current := sum_b w[b] * current[b*m + i], m = length / 2^k[j]) and, where k_next[j] != 0,
+ * writes the 2^k_next[j] block sums of the result; read_tail writes each current table (m[j] canonical values).  Each
+ * returns a zigz_status; the first that is not ZIGZ_OK ends the run with it.  No GPU is touched. */
+typedef zigz_status (*zigz_radix_batch_sums_fn)(void *user, size_t count, const size_t *tables, const unsigned *k,
+                                                uint64_t *sums);
+typedef zigz_status (*zigz_radix_batch_fold_fn)(void *user, size_t count, const size_t *tables, const unsigned *k,
+                                                const uint64_t *weights, const unsigned *k_next, uint64_t *next_sums);
+typedef zigz_status (*zigz_radix_batch_tail_fn)(void *user, size_t count, const size_t *tables, const size_t *m, uint64_t *out);
+zigz_status zigz_sumcheck_radix_run_batch(void *user, zigz_radix_batch_sums_fn block_sums, zigz_radix_batch_fold_fn fold,
+                                          zigz_radix_batch_tail_fn read_tail, size_t k, const size_t *ns,
+                                          const uint64_t *fixed_challenges, uint64_t *rounds, uint64_t *points,
+                                          uint64_t *final_evals);
+
 /* ---------------------------------------------------------------- host SHA3 sponge / transcript
  * FiatShamirTranscript   src/core/hash.zig:255-324 (sequential by construction: stays on the host) */
 zigz_transcript *zigz_transcript_new(void);

@@ -57,6 +57,11 @@ class RadixOps(C.Structure):  # zigz_radix_ops
     _fields_ = [("user", vp), ("block_sums", RADIX_BLOCK_SUMS_FN), ("fold", RADIX_FOLD_FN), ("read_tail", RADIX_READ_TAIL_FN)]
 
 
+RB_BLOCK_SUMS_FN = C.CFUNCTYPE(C.c_int32, vp, C.c_size_t, szp, C.POINTER(C.c_uint), u64p)  # zigz_radix_batch_sums_fn
+RB_FOLD_FN = C.CFUNCTYPE(C.c_int32, vp, C.c_size_t, szp, C.POINTER(C.c_uint), u64p, C.POINTER(C.c_uint), u64p)
+RB_READ_TAIL_FN = C.CFUNCTYPE(C.c_int32, vp, C.c_size_t, szp, szp, u64p)
+
+
 # name -> (restype, argtypes).  Every symbol include/zigz_hip.h declares must appear here
 # (tests/test_abi.py cross-checks this table against the header and the shared object).
 SIGNATURES = {
@@ -135,6 +140,12 @@ SIGNATURES = {
     "zigz_rccl_comm_rank": (C.c_int, [vp]),
     "zigz_rccl_comm_world": (C.c_int, [vp]),
     "zigz_rccl_comm_destroy": (None, [vp]),
+    "zigz_dev_sumcheck_prove_batch": (C.c_int32, [vp, C.POINTER(vp), szp, C.c_size_t, u64p, u64p, u64p, u64p, szp]),
+    "zigz_sumcheck_prove_batch": (C.c_int32, [vp, C.POINTER(u64p), szp, C.c_size_t, u64p, u64p, u64p, u64p, szp]),
+    "zigz_lasso_prove_batch": (C.c_int32, [vp, C.c_size_t, C.POINTER(u64p), szp, C.POINTER(u64p), szp, szp, szp, C.POINTER(u64p), szp,
+                                           szp, C.POINTER(u64p), C.POINTER(u64p), u64p, u8p, u8p, szp]),
+    "zigz_sumcheck_radix_run_batch": (C.c_int32, [vp, RB_BLOCK_SUMS_FN, RB_FOLD_FN, RB_READ_TAIL_FN, C.c_size_t, szp, u64p, u64p, u64p,
+                                                  u64p]),
     "zigz_dev_sumcheck_prove_rccl": (C.c_int32, [vp, vp, C.c_size_t, vp, u64p, u64p, u64p]),
     "zigz_transcript_new": (vp, []),
     "zigz_transcript_free": (None, [vp]),

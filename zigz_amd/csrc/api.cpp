@@ -183,6 +183,7 @@ extern "C" void zigz_ctx_destroy(zigz_ctx *ctx) {
     if (ctx->d_run_aux) (void)hipFree(ctx->d_run_aux);
     if (ctx->d_cons_aux) (void)hipFree(ctx->d_cons_aux);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
+    if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
     if (ctx->h_roots) (void)hipHostFree(ctx->h_roots);
     for (int i = 0; i < 6; i++)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);

@@ -17,6 +17,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <deque>
@@ -315,5 +316,66 @@ bool host_sponge_absorb_tagged(uint64_t st[25], size_t *pos, const uint8_t *tag,
 }
 
 void host_keccak_permute_x8(uint64_t st[25][8]) { keccak_f1600_x8(st); }
+
+// Flat SHA3 commitments (commitToPolynomial, src/lookups/lasso_prover.zig:242-252: one LE64 word per value) of `count`
+// independent value lists, e.g. the table and query fingerprints of a batch of Lasso proofs.  With AVX-512F the lists go
+// in groups of 8 of similar length, each group on a thread of its own: the full 136-byte blocks of its 8 sponges are absorbed
+// in lock step by one 8-way permutation per block, and each sponge's last partial block and padding are finished on its own
+// (Sha3_256 over the extracted state).  Without it, one thread per list runs the sequential sponge.  The digests equal
+// those of Sha3_256::update_le64 over each list, byte for byte.
+void flat_commit_batch(const uint32_t *const *ev, const size_t *n, size_t count, uint8_t (*out)[32]) {
+    constexpr size_t WORDS = RATE / 8;  // 17 values per block
+    auto one = [&](size_t i) {
+        Sha3_256 h;
+        for (size_t j = 0; j < n[i]; j++) h.update_le64(ev[i][j]);
+        h.finalize(out[i]);
+    };
+    std::vector<std::thread> th;
+    if (!cpu_has_avx512f()) {
+        th.reserve(count);
+        for (size_t i = 0; i < count; i++) th.emplace_back(one, i);
+        for (auto &t : th) t.join();
+        return;
+    }
+    std::vector<size_t> order(count);
+    for (size_t i = 0; i < count; i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return n[a] > n[b]; });
+    auto group = [&](size_t g0) {
+        const size_t ns = count - g0 < (size_t)SLOTS ? count - g0 : (size_t)SLOTS;
+        alignas(64) uint64_t st[25][SLOTS];
+        memset(st, 0, sizeof(st));
+        size_t full[SLOTS] = {0};
+        size_t blocks = 0;
+        for (size_t s = 0; s < ns; s++) {
+            full[s] = n[order[g0 + s]] / WORDS;
+            if (full[s] > blocks) blocks = full[s];
+        }
+        auto finish = [&](size_t s) {  // the sponge's remaining values and padding, from its lane of the state
+            const size_t i = order[g0 + s];
+            Sha3_256 h;
+            for (int l = 0; l < 25; l++) h.raw_state()[l] = st[l][s];
+            *h.raw_pos() = 0;
+            for (size_t j = full[s] * WORDS; j < n[i]; j++) h.update_le64(ev[i][j]);
+            h.finalize(out[i]);
+        };
+        for (size_t s = 0; s < ns; s++)
+            if (full[s] == 0) finish(s);
+        for (size_t b = 0; b < blocks; b++) {
+            for (size_t s = 0; s < ns; s++) {
+                if (b >= full[s]) continue;
+                const uint32_t *v = ev[order[g0 + s]] + b * WORDS;
+                for (size_t w = 0; w < WORDS; w++) st[w][s] ^= v[w];
+            }
+            keccak_f1600_x8(st);
+            for (size_t s = 0; s < ns; s++)
+                if (full[s] == b + 1) finish(s);
+        }
+    };
+    const size_t groups = (count + SLOTS - 1) / SLOTS;
+    th.reserve(groups);
+    for (size_t g = 1; g < groups; g++) th.emplace_back(group, g * SLOTS);
+    group(0);
+    for (auto &t : th) t.join();
+}
 
 }  // namespace zk

@@ -409,4 +409,48 @@ void launch_lasso_fingerprints(const uint32_t *d_rows, size_t rows, size_t width
 // synthetic canonical table for the measurement hooks: out[i] = splitmix-style hash of (seed, i) mod p
 void launch_fill_pattern(uint32_t *d_out, size_t n, uint32_t seed, hipStream_t s);
 
+// ---- batched radix sumcheck (sumcheck_batch.hip): several tables of different lengths in one launch per pass.
+constexpr unsigned BATCH_WG = 256;  // threads per workgroup of every batch launch (the launchers' workgroup counts use it)
+// One descriptor per table of a pass; the workgroups of table j are [first_wg, first_wg of table j + 1).  All pointers are
+// device pointers; every table is 16-byte aligned and has 2^log2_n elements.
+struct BatchTab {
+    const uint32_t *in;        // the table this pass reads
+    uint32_t *out;             // finalize: the folded table (2^(log2_n - k) values)
+    unsigned long long *part;  // fold / finalize: groups x m exact partial sums
+    unsigned long long *sums;  // block sums pass: the table's 2^k sums; finalize: the next stage's 2^(log2_n - k - log2_m2)
+    const uint32_t *w;         // fold: the 2^k eq weights, Montgomery form
+    uint64_t tail_off;         // tails pass: first word of the table's values in the published u32 array
+    uint32_t log2_n;           // length of `in`
+    uint32_t k;                // 2^k blocks (block sums) / rows (fold, finalize)
+    uint32_t log2_m2;          // finalize: block size of the next stage's sums (0: the table has no next stage)
+    uint32_t iters;            // block sums: 16-byte chunks per lane (a wave's range lies inside one block)
+    uint32_t first_wg;
+    uint32_t reserved;
+};
+// What a publishing launch hands to the host: n u64 sums from d_sums (left zero) into pinned h_dst (k_batch_publish), or the
+// tables' values (k_batch_tails); every workgroup writes its share, and the last one to finish stores `seq` into the pinned
+// word `flag` (`count`: a device word that is zero between launches).
+struct BatchPublish {
+    void *h_dst = nullptr;
+    unsigned long long *d_sums = nullptr;
+    size_t n = 0;
+    unsigned *count = nullptr;
+    unsigned long long *flag = nullptr;
+    unsigned long long seq = 0;
+};
+void launch_batch_block_sums(const BatchTab *d_tabs, unsigned nt, unsigned nwg, hipStream_t s);
+void launch_batch_fold(const BatchTab *d_tabs, unsigned nt, unsigned nwg, hipStream_t s);
+void launch_batch_finalize(const BatchTab *d_tabs, unsigned nt, unsigned nwg, hipStream_t s);
+void launch_batch_publish(const BatchPublish &pub, hipStream_t s);
+void launch_batch_tails(const BatchTab *d_tabs, unsigned nt, unsigned nwg, const BatchPublish &pub, hipStream_t s);
+// Lasso fingerprints of several instances (K9 per row): rows x width canonical u32 at `in` -> out[rows], then zeros up to
+// `padded` (the queries' ceilPow2 padding, lasso_prover.zig:139-142; tables: padded == rows)
+struct FpTab {
+    const uint32_t *in;
+    uint32_t *out;
+    uint64_t rows, padded;
+    uint32_t width, first_wg;
+};
+void launch_batch_fingerprints(const FpTab *d_tabs, unsigned nt, unsigned nwg, hipStream_t s);
+
 }  // namespace zk

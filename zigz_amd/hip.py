@@ -357,6 +357,102 @@ class Context:
         self.check(lib.zigz_dev_sumcheck_prove_rccl(self.h, vp(d_local), n_local, comm.h, rp, ptp, C.byref(fe)))
         return r[: 2 * nv].copy(), pt[:nv].copy(), fe.value
 
+    # ---- batched provers (k independent tables per call, shared launches)
+    def check_batch(self, rc, bad):
+        """check() for the batch entries: the exception carries the index of the first failing table as .bad_index"""
+        if rc != 0:
+            e = errors.ZigzError(rc, _name(rc), lib.zigz_last_error(self.h).decode(errors="replace"))
+            e.bad_index = bad.value
+            raise e
+
+    @staticmethod
+    def _batch_out(ns):
+        nvs = [max(int(n).bit_length() - 1, 0) for n in ns]
+        tot = sum(nvs)
+        r, rp = _out_u64(2 * tot)
+        pt, ptp = _out_u64(tot)
+        fe, fep = _out_u64(len(ns))
+        return nvs, (r, rp), (pt, ptp), (fe, fep)
+
+    @staticmethod
+    def _batch_split(nvs, r, pt, fe):
+        out, o = [], 0
+        for i, v in enumerate(nvs):
+            out.append((r[2 * o: 2 * (o + v)].copy(), pt[o: o + v].copy(), int(fe[i])))
+            o += v
+        return out
+
+    def sumcheck_prove_batch(self, tables, challenges=None):
+        """zigz_sumcheck_prove_batch: sumcheck_prove(t[, challenges[i]]) for every table, in shared launches.
+        Returns the list of (rounds, point, final_eval)."""
+        k = len(tables)
+        arrs = [_u64(t) for t in tables]
+        ns = (C.c_size_t * max(k, 1))(*[len(t) for t in tables])
+        ptrs = (u64p * max(k, 1))(*[p for _, p in arrs])
+        nvs, (r, rp), (pt, ptp), (fe, fep) = self._batch_out([len(t) for t in tables])
+        cp = None
+        if challenges is not None:
+            c, cp = _u64(np.concatenate([np.asarray(x, dtype=np.uint64).reshape(-1) for x in challenges] + [np.zeros(0, np.uint64)]))
+        bad = C.c_size_t(0)
+        self.check_batch(lib.zigz_sumcheck_prove_batch(self.h, ptrs, ns, k, cp, rp, ptp, fep, C.byref(bad)), bad)
+        return self._batch_split(nvs, r, pt, fe)
+
+    def dev_sumcheck_prove_batch(self, d_tables, ns, challenges=None):
+        """zigz_dev_sumcheck_prove_batch over device-resident tables (packed u32 canonical, 16-byte aligned)."""
+        k = len(ns)
+        nsa = (C.c_size_t * max(k, 1))(*[int(n) for n in ns])
+        ptrs = (vp * max(k, 1))(*[int(d) for d in d_tables])
+        nvs, (r, rp), (pt, ptp), (fe, fep) = self._batch_out(ns)
+        cp = None
+        if challenges is not None:
+            c, cp = _u64(np.concatenate([np.asarray(x, dtype=np.uint64).reshape(-1) for x in challenges] + [np.zeros(0, np.uint64)]))
+        bad = C.c_size_t(0)
+        self.check_batch(lib.zigz_dev_sumcheck_prove_batch(self.h, ptrs, nsa, k, cp, rp, ptp, fep, C.byref(bad)), bad)
+        return self._batch_split(nvs, r, pt, fe)
+
+    def lasso_prove_batch(self, instances):
+        """zigz_lasso_prove_batch: instances are dicts with table, queries and optional n_in (2), n_out (1), mapping (None).
+        Returns the list of lasso_prove() dicts."""
+        k = len(instances)
+        n = max(k, 1)
+        keep = []
+        tabs, qs, maps, routs, pouts = (u64p * n)(), (u64p * n)(), (u64p * n)(), (u64p * n)(), (u64p * n)()
+        rows, nqs, nins, nouts, nmaps = [(C.c_size_t * n)() for _ in range(5)]
+        outs = []
+        for i, d in enumerate(instances):
+            n_in, n_out = d.get("n_in", 2), d.get("n_out", 1)
+            w = n_in + n_out
+            t, tabs[i] = _u64(np.asarray(d["table"], dtype=np.uint64).reshape(-1))
+            q, qs[i] = _u64(np.asarray(d["queries"], dtype=np.uint64).reshape(-1))
+            rows[i] = 0 if len(d["table"]) == 0 or w == 0 else len(np.asarray(d["table"]).reshape(-1)) // w
+            nqs[i] = nq = len(d["queries"])
+            nins[i], nouts[i] = n_in, n_out
+            npad = 1
+            while npad < max(nq, 1):
+                npad <<= 1
+            nvmax = npad.bit_length() - 1
+            r, routs[i] = _out_u64(2 * nvmax)
+            pt, pouts[i] = _out_u64(nvmax)
+            keep += [t, q]
+            if d.get("mapping") is not None:
+                m, maps[i] = _u64(d["mapping"])
+                nmaps[i] = len(d["mapping"])
+                keep.append(m)
+            outs.append((r, pt))
+        nv = (C.c_size_t * n)()
+        fe, fep = _out_u64(n)
+        qc, qcp = _out_u8(32 * n)
+        tc, tcp = _out_u8(32 * n)
+        bad = C.c_size_t(0)
+        self.check_batch(lib.zigz_lasso_prove_batch(self.h, k, tabs, rows, qs, nqs, nins, nouts, maps, nmaps, nv, routs, pouts, fep,
+                                                    qcp, tcp, C.byref(bad)), bad)
+        out = []
+        for i, (r, pt) in enumerate(outs):
+            v = nv[i]
+            out.append(dict(nv=v, rounds=r[: 2 * v].copy(), point=pt[:v].copy(), final_eval=int(fe[i]),
+                            query_commit=qc[32 * i: 32 * i + 32].tobytes(), table_commit=tc[32 * i: 32 * i + 32].tobytes()))
+        return out
+
     # ---- Lasso
     def lasso_fingerprints(self, rows):
         rows = np.ascontiguousarray(rows, dtype=np.uint64)

@@ -316,6 +316,88 @@ def sumcheck_radix_run(py_ops, n_local, dist, challenges=None, allgather=None, r
     return np.array(r[: 2 * nv], dtype=np.uint64), np.array(pt[:nv], dtype=np.uint64), fe.value
 
 
+def sumcheck_radix_run_batch(py_ops, ns, challenges=None):
+    """The batched C++ orchestration (zigz_sumcheck_radix_run_batch) over Python data passes that serve several tables at
+    once: py_ops.block_sums(tables, ks) -> one list of 2^ks[j] ints per table, py_ops.fold(tables, ks, weights, k_next) ->
+    one list of 2^k_next[j] ints per table (None where k_next[j] == 0; weights[j] holds table j's 2^ks[j] weights),
+    py_ops.read_tail(tables, ms) -> one list of ms[j] ints per table.  challenges: None or one list per table.
+    Returns the list of (rounds, point, final_eval).  No GPU is touched: the CPU tests drive the batch schedule with it."""
+    import ctypes as C
+    from . import _ffi
+    k = len(ns)
+    err = []
+
+    def guard(fn):
+        def w(*a):
+            try:
+                return int(fn(*a) or 0)
+            except Exception as e:  # never unwind into C
+                err.append(e)
+                return 103
+        return w
+
+    def c_block_sums(_u, count, tables, ks, out):
+        tl, kl = [tables[j] for j in range(count)], [ks[j] for j in range(count)]
+        v = py_ops.block_sums(tl, kl)
+        if isinstance(v, int):
+            return v
+        o = 0
+        for j in range(count):
+            for x in v[j][: 1 << kl[j]]:
+                out[o] = int(x)
+                o += 1
+
+    def c_fold(_u, count, tables, ks, w, knext, nxt):
+        tl, kl, kn = [tables[j] for j in range(count)], [ks[j] for j in range(count)], [knext[j] for j in range(count)]
+        ws, o = [], 0
+        for j in range(count):
+            ws.append([int(w[o + b]) for b in range(1 << kl[j])])
+            o += 1 << kl[j]
+        v = py_ops.fold(tl, kl, ws, kn)
+        if isinstance(v, int):
+            return v
+        o = 0
+        for j in range(count):
+            if kn[j]:
+                for x in v[j][: 1 << kn[j]]:
+                    nxt[o] = int(x)
+                    o += 1
+
+    def c_read_tail(_u, count, tables, ms, out):
+        tl, ml = [tables[j] for j in range(count)], [ms[j] for j in range(count)]
+        v = py_ops.read_tail(tl, ml)
+        if isinstance(v, int):
+            return v
+        o = 0
+        for j in range(count):
+            for x in v[j][: ml[j]]:
+                out[o] = int(x)
+                o += 1
+
+    cbs = (_ffi.RB_BLOCK_SUMS_FN(guard(c_block_sums)), _ffi.RB_FOLD_FN(guard(c_fold)), _ffi.RB_READ_TAIL_FN(guard(c_read_tail)))
+    nvs = [max(int(n).bit_length() - 1, 0) for n in ns]
+    tot = sum(nvs)
+    r = (C.c_uint64 * max(2 * tot, 1))()
+    pt = (C.c_uint64 * max(tot, 1))()
+    fe = (C.c_uint64 * max(k, 1))()
+    nsa = (C.c_size_t * max(k, 1))(*[int(n) for n in ns])
+    ch = None
+    if challenges is not None:
+        flat = [int(c) for cs in challenges for c in cs]
+        ch = (C.c_uint64 * max(len(flat), 1))(*flat)
+    rc = _ffi.lib.zigz_sumcheck_radix_run_batch(None, *cbs, k, nsa, ch, r, pt, fe)
+    if err:
+        raise err[0]
+    if rc != 0:
+        from . import errors
+        raise errors.ZigzError(rc, _ffi.lib.zigz_status_name(rc).decode())
+    out, o = [], 0
+    for i, v in enumerate(nvs):
+        out.append((np.array(r[2 * o: 2 * (o + v)], dtype=np.uint64), np.array(pt[o: o + v], dtype=np.uint64), fe[i]))
+        o += v
+    return out
+
+
 def sumcheck_prove_row_sharded(ops, local_table, n_global, dist, transcript_factory):
     """SumcheckProver.prove (src/proofs/sumcheck_prover.zig:26-91) over a table sharded by rows (interleaved).
     `local_table`: ops-specific handle of this rank's n_global/G elements.  One all-reduce of 2 words per round.
