@@ -24,11 +24,11 @@ OUT = os.path.join(ROOT, "profiles", "isa_counts.json")
 SOURCES = ("kernels.hip", "merkle_levels.hip")
 
 
-def assembly(extra=()):
+def assembly(extra=(), sources=SOURCES):
     hipcc = "/opt/rocm/bin/hipcc"
     out = []
     with tempfile.TemporaryDirectory() as d:
-        for src in SOURCES:
+        for src in sources:
             s = os.path.join(d, src + ".s")
             subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{ROOT}/include", f"-I{CSRC}",
                                    "--cuda-device-only", "-S", "-o", s, os.path.join(CSRC, src), *extra,

@@ -1056,6 +1056,21 @@ __device__ __forceinline__ void signal_done(const DoneFlag &done, unsigned n_gro
         }
     }
 }
+// The same for workgroups of several waves: thread 0 may count its workgroup only once every wave has fenced its stores, so
+// a barrier sits between the fences and the count (without it the host could see the completion word while another wave's
+// words are still on their way).  Every thread of the workgroup must call it.
+__device__ __forceinline__ void signal_done_block(const DoneFlag &done, unsigned n_groups) {
+    if (!done.flag) return;
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned prev = atomicAdd(done.count, 1u);
+        if (prev == n_groups - 1) {
+            *done.count = 0;
+            __hip_atomic_store(done.flag, done.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
 
 __global__ __launch_bounds__(64) void k_paths(TreeRef t, size_t n_values, unsigned height, const uint32_t *__restrict__ vals,
                                               size_t val_stride, const uint64_t *__restrict__ idx, uint8_t *__restrict__ sib,
@@ -1113,8 +1128,9 @@ __global__ void k_gather_nodes(const uint8_t *__restrict__ tree, size_t tree_str
 }
 // roots of a commit job + the build's counters behind them (kernels.hpp: JOB_SUMMARY_WORDS u64; a null pointer reads as 0): ONE
 // buffer, one copy
-__global__ void k_job_summary(TreeRef t, unsigned height, uint8_t *__restrict__ out, size_t ncols, const unsigned long long *r_ctr,
-                              const unsigned long long *sd_ctr, const unsigned long long *g_ctr, DoneFlag done) {
+__global__ __launch_bounds__(64) void k_job_summary(TreeRef t, unsigned height, uint8_t *__restrict__ out, size_t ncols,
+                                                    const unsigned long long *r_ctr, const unsigned long long *sd_ctr,
+                                                    const unsigned long long *g_ctr, DoneFlag done) {
     ZK_PRIO_SMALL();
     const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     // a batched job (proof blockIdx.y of gridDim.y): the roots of all proofs one after the other, then every proof's counters
@@ -1176,7 +1192,7 @@ __global__ __launch_bounds__(TPB) void k_publish(void *d_src, size_t n, void *h_
             if (rezero) s[i] = 0;
         }
     }
-    signal_done(done, gridDim.x);
+    signal_done_block(done, gridDim.x);  // (TPB threads: several waves; no thread returns early)
 }
 void launch_publish_u64(unsigned long long *d_src, size_t n, unsigned long long *h_dst, bool rezero, hipStream_t s, DoneFlag done) {
     hipLaunchKernelGGL(k_publish<8>, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, s, (void *)d_src, n, (void *)h_dst, rezero ? 1 : 0, done);
