@@ -71,6 +71,7 @@ typedef struct zigz_ctx zigz_ctx;
 typedef struct zigz_merkle zigz_merkle;         /* one committed column: all tree levels in HBM */
 typedef struct zigz_commit_job zigz_commit_job; /* a batch of columns going through commit -> open */
 typedef struct zigz_transcript zigz_transcript; /* host-side SHA3 Fiat-Shamir sponge */
+typedef struct zigz_merkle_batch zigz_merkle_batch; /* k committed tables: their values and trees in one allocation */
 
 /* ---------------------------------------------------------------- context */
 uint32_t zigz_abi_version(void);
@@ -461,6 +462,36 @@ zigz_status zigz_sumcheck_radix_run_batch(void *user, zigz_radix_batch_sums_fn b
                                           zigz_radix_batch_tail_fn read_tail, size_t k, const size_t *ns,
                                           const uint64_t *fixed_challenges, uint64_t *rounds, uint64_t *points,
                                           uint64_t *final_evals);
+
+/* k independent SimpleMerkleTree.build calls (merkle_tree.zig:283-318; CommitmentScheme.batchCommit,
+ * polynomial_commit.zig:132-157) in shared launches: ceil(max height / 9) build launches and one hand-off for the whole batch.
+ * Table i has ns[i] >= 1 values of any length (padded with hashLeaf(0), like zigz_merkle_commit).  Outputs: roots (k * 32
+ * bytes), heights[k]; every root is byte-identical to the single call's.  out == NULL: roots only (the trees are freed);
+ * otherwise *out owns the values and trees of all k tables in ONE device allocation until zigz_merkle_batch_destroy.
+ * The batch builds densely: the context's hint options, zigz_kernel_stats and an active commit job are neither read nor
+ * changed (the calls queue behind the job on the context's stream).  k <= ZIGZ_BATCH_MAX, else ZIGZ_ERR_INVALID_ARGUMENT;
+ * k == 0 returns ZIGZ_OK and touches nothing.  Every argument is checked before anything runs: on the first table the single
+ * call would reject, the call returns that status, writes the table's index to *bad_index (if non-NULL), launches nothing
+ * and leaves the outputs untouched.
+ * Device form: d_values[i] are packed-u32 canonical values (not checked), 4-byte aligned; the same table may repeat. */
+zigz_status zigz_dev_merkle_commit_batch(zigz_ctx *ctx, const uint32_t *const *d_values, const size_t *ns, size_t k,
+                                         uint8_t *roots, size_t *heights, zigz_merkle_batch **out, size_t *bad_index);
+/* host form: canonical u64 (ZIGZ_ERR_NOT_CANONICAL otherwise), uploaded in one copy */
+zigz_status zigz_merkle_commit_batch(zigz_ctx *ctx, const uint64_t *const *values, const size_t *ns, size_t k,
+                                     uint8_t *roots, size_t *heights, zigz_merkle_batch **out, size_t *bad_index);
+/* tree_i.open(indices[i]) for every tree of the batch (merkle_tree.zig:324-360): siblings (32 B each) and dirs are packed
+ * tree by tree, tree i at offset sum_{j<i} heights[j]; leaf_values[k].  One launch, one hand-off. */
+zigz_status zigz_merkle_open_batch(zigz_ctx *ctx, const zigz_merkle_batch *b, const uint64_t *indices, uint8_t *siblings,
+                                   uint8_t *dirs, uint64_t *leaf_values, size_t *bad_index);
+/* CommitmentScheme.open(poly_i, tree_i, point_i) for every tree (polynomial_commit.zig:86-115): table i must have 2^v values
+ * (ZIGZ_ERR_LENGTH_NOT_POWER_OF_TWO otherwise); points are concatenated, heights[i] canonical coordinates each; values[i] =
+ * eval(point_i) over the stored values, indices[i] = pointToIndex(point_i) (:178-183), then the path as above.  One eval
+ * launch, one path launch, one hand-off. */
+zigz_status zigz_commit_open_batch(zigz_ctx *ctx, const zigz_merkle_batch *b, const uint64_t *points, uint64_t *values,
+                                   uint64_t *indices, uint8_t *siblings, uint8_t *dirs, uint64_t *leaf_values,
+                                   size_t *bad_index);
+/* waits for the context's stream, then frees the batch (NULL: no-op) */
+void zigz_merkle_batch_destroy(zigz_ctx *ctx, zigz_merkle_batch *b);
 
 /* ---------------------------------------------------------------- host SHA3 sponge / transcript
  * FiatShamirTranscript   src/core/hash.zig:255-324 (sequential by construction: stays on the host) */

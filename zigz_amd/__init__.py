@@ -6,8 +6,8 @@ fails loudly (ImportError) if they are missing; there is no CPU fallback.  `zigz
 importable without the libraries (it is what produces them)."""
 import importlib
 
-_HIP_NAMES = {"P", "NUM_COLUMNS", "CommitJob", "CommitmentScheme", "Context", "SimpleMerkleTree", "Transcript",
-              "device_count", "sha256", "sha3_256"}
+_HIP_NAMES = {"P", "NUM_COLUMNS", "CommitJob", "CommitmentScheme", "Context", "MerkleBatch", "SimpleMerkleTree",
+              "Transcript", "device_count", "sha256", "sha3_256"}
 
 
 def __getattr__(name):

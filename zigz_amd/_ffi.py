@@ -144,6 +144,11 @@ SIGNATURES = {
     "zigz_sumcheck_prove_batch": (C.c_int32, [vp, C.POINTER(u64p), szp, C.c_size_t, u64p, u64p, u64p, u64p, szp]),
     "zigz_lasso_prove_batch": (C.c_int32, [vp, C.c_size_t, C.POINTER(u64p), szp, C.POINTER(u64p), szp, szp, szp, C.POINTER(u64p), szp,
                                            szp, C.POINTER(u64p), C.POINTER(u64p), u64p, u8p, u8p, szp]),
+    "zigz_dev_merkle_commit_batch": (C.c_int32, [vp, C.POINTER(vp), szp, C.c_size_t, u8p, szp, C.POINTER(vp), szp]),
+    "zigz_merkle_commit_batch": (C.c_int32, [vp, C.POINTER(u64p), szp, C.c_size_t, u8p, szp, C.POINTER(vp), szp]),
+    "zigz_merkle_open_batch": (C.c_int32, [vp, vp, u64p, u8p, u8p, u64p, szp]),
+    "zigz_commit_open_batch": (C.c_int32, [vp, vp, u64p, u64p, u64p, u8p, u8p, u64p, szp]),
+    "zigz_merkle_batch_destroy": (None, [vp, vp]),
     "zigz_sumcheck_radix_run_batch": (C.c_int32, [vp, RB_BLOCK_SUMS_FN, RB_FOLD_FN, RB_READ_TAIL_FN, C.c_size_t, szp, u64p, u64p, u64p,
                                                   u64p]),
     "zigz_dev_sumcheck_prove_rccl": (C.c_int32, [vp, vp, C.c_size_t, vp, u64p, u64p, u64p]),

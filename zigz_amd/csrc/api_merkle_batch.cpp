@@ -1,0 +1,391 @@
+// C ABI of libzigz_hip.so, part 6: batched Merkle commitments -- k independent SimpleMerkleTree builds, openings and
+// CommitmentScheme openings in shared launches (merkle_batch.hip).
+//
+// One call to zigz_merkle_commit costs two allocations, an upload with its own round trip, a leaf launch and one launch per
+// level, and another round trip for the root; a 2^10-leaf tree is ~2 K permutations, well under a microsecond of the chip, so
+// a caller committing many small tables pays almost only for that.  Here a batch makes one device allocation (descriptors,
+// values, trees and the eval accumulators of all k tables), one upload, ceil(max height / 9) build launches and one launch that
+// publishes the roots into pinned memory; an opening is one copy of descriptors, (an eval launch,) one path launch and one
+// hand-off.  Every tree is the dense tree of the single call, node for node, so roots and paths are byte-identical to it.
+#include "api_internal.hpp"
+
+#include <algorithm>
+
+using namespace zk;
+
+struct zigz_merkle_batch {
+    zigz_ctx *ctx;
+    size_t k;
+    std::vector<uint64_t> n, npad;
+    std::vector<unsigned> height;
+    std::vector<size_t> vals_off;  // u32 words into d_vals (every table 16-byte aligned)
+    std::vector<size_t> tree_off;  // nodes into d_tree (2 npad per tree)
+    std::vector<size_t> sib_off;   // sum of the heights before the tree
+    size_t sum_h;
+    void *d_mem;                   // the one allocation: descriptors | values | accumulators | trees
+    uint8_t *d_desc;
+    size_t desc_bytes;
+    uint32_t *d_vals;
+    unsigned long long *d_acc;     // k words, zero between calls
+    uint8_t *d_tree;
+};
+
+namespace {
+
+constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+constexpr size_t MAX_VALUES = (size_t)1 << 40;  // merkle_tree.zig:287 (the single call's device-size cap)
+
+unsigned stages_of(unsigned h) { return h <= MB_STAGE_LEVELS ? 1 : (h + MB_STAGE_LEVELS - 1) / MB_STAGE_LEVELS; }
+size_t open_desc_bytes(size_t k, size_t sum_h) {
+    return align256(k * sizeof(MPathTab)) + align256(k * sizeof(MEvalTab)) + 2 * sum_h * sizeof(uint32_t);
+}
+
+zigz_status fail_at(size_t *bad_index, size_t i, zigz_status st) {
+    if (bad_index) *bad_index = i;
+    return st;
+}
+
+// pinned host memory for one call: the context's staging buffer when it fits, else the (grown, never shrunk) batch region
+zigz_status pinned(zigz_ctx *ctx, size_t bytes, uint8_t **out) {
+    if (bytes <= PIN_WORDS * 8) {
+        *out = (uint8_t *)ctx->h_pin;
+        return ZIGZ_OK;
+    }
+    if (ctx->h_batch_bytes < bytes) {
+        if (ctx->h_batch) {
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            (void)hipHostFree(ctx->h_batch);
+            ctx->h_batch = nullptr;
+            ctx->h_batch_bytes = 0;
+        }
+        const size_t want = align256(bytes + bytes / 8);
+        HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_batch, want, hipHostMallocDefault));
+        ctx->h_batch_bytes = want;
+    }
+    *out = (uint8_t *)ctx->h_batch;
+    return ZIGZ_OK;
+}
+
+// waits for what a launch publishes under `done` (a short spin, then the runtime's wait, which also reports a fault)
+zigz_status wait_done(zigz_ctx *ctx, const DoneFlag &done) {
+    const bool seen = g_sleep_wait.load() ? sleep_wait(done.flag, done.seq) : spin_wait(done.flag, done.seq);
+    if (!seen) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return ZIGZ_OK;
+}
+
+// Narrows the host tables into the packed u32 staging (table i at word vals_off[i]) and finds the first table holding a
+// value >= p among the first `count` (count: none).  Large batches are split into chunks over up to 8 threads.
+size_t narrow_tables(const uint64_t *const *values, const size_t *ns, size_t count, const std::vector<size_t> &off, uint32_t *dst) {
+    constexpr size_t CHUNK = (size_t)1 << 18;
+    struct Piece {
+        size_t t, lo, hi;
+    };
+    std::vector<Piece> pieces;
+    size_t total = 0;
+    for (size_t i = 0; i < count; i++) {
+        for (size_t lo = 0; lo < ns[i]; lo += CHUNK) pieces.push_back(Piece{i, lo, std::min(ns[i], lo + CHUNK)});
+        total += ns[i];
+    }
+    std::vector<uint8_t> bad(pieces.size(), 0);
+    auto run = [&](size_t j) {
+        const Piece &p = pieces[j];
+        const uint64_t *src = values[p.t];
+        uint32_t *d = dst + off[p.t];
+        uint64_t any = 0;
+        for (size_t x = p.lo; x < p.hi; x++) {
+            const uint64_t v = src[x];
+            any |= (uint64_t)(v >= P);
+            d[x] = (uint32_t)v;
+        }
+        bad[j] = (uint8_t)any;
+    };
+    unsigned nt = (unsigned)std::min<size_t>(8, total / (1 << 20));
+    const unsigned hw = std::thread::hardware_concurrency();
+    if (hw && nt > hw) nt = hw;
+    if (nt <= 1) {
+        for (size_t j = 0; j < pieces.size(); j++) run(j);
+    } else {
+        std::atomic<size_t> next{0};
+        auto work = [&] {
+            for (size_t j; (j = next.fetch_add(1)) < pieces.size();) run(j);
+        };
+        std::vector<std::thread> th;
+        for (unsigned t = 1; t < nt; t++) th.emplace_back(work);
+        work();
+        for (auto &t : th) t.join();
+    }
+    for (size_t j = 0; j < pieces.size(); j++)
+        if (bad[j]) return pieces[j].t;
+    return count;
+}
+
+// the single call's checks of table i before its upload (zigz_merkle_commit)
+zigz_status table_pre(size_t n, const void *p, bool dev) {
+    if (n == 0) return ZIGZ_ERR_EMPTY_VALUES;              // merkle_tree.zig:284
+    if (n > MAX_VALUES) return ZIGZ_ERR_TOO_MANY_VALUES;   // merkle_tree.zig:287
+    if (!p || (dev && ((uintptr_t)p & 3))) return ZIGZ_ERR_INVALID_ARGUMENT;
+    return ZIGZ_OK;
+}
+
+void batch_free(zigz_ctx *ctx, zigz_merkle_batch *b) {
+    if (!b) return;
+    if (ctx) (void)hipStreamSynchronize(ctx->stream);
+    if (b->d_mem) (void)hipFree(b->d_mem);
+    delete b;
+}
+
+// Builds the k trees.  Exactly one of d_values (device tables) and values (host tables) is given; the host tables are narrowed
+// into pinned memory and checked (< p) before anything is allocated on the device or launched.
+zigz_status commit_run(zigz_ctx *ctx, const uint32_t *const *d_values, const uint64_t *const *values, const size_t *ns, size_t k,
+                       uint8_t *roots, size_t *heights, zigz_merkle_batch **out, size_t *bad_index) {
+    ZIGZ_NOTHROW_BEGIN
+    zigz_merkle_batch *b = new zigz_merkle_batch();
+    b->ctx = ctx;
+    b->k = k;
+    b->n.assign(ns, ns + k);
+    b->npad.resize(k);
+    b->height.resize(k);
+    b->vals_off.resize(k);
+    b->tree_off.resize(k);
+    b->sib_off.resize(k);
+    size_t vw = 0, nodes = 0, sum_h = 0;
+    unsigned max_stages = 1;
+    for (size_t i = 0; i < k; i++) {
+        b->npad[i] = ceil_pow2(ns[i]);
+        b->height[i] = log2_floor(b->npad[i]);
+        b->vals_off[i] = vw;
+        vw += (ns[i] + 3) & ~(size_t)3;
+        b->tree_off[i] = nodes;
+        nodes += 2 * b->npad[i];
+        b->sib_off[i] = sum_h;
+        sum_h += b->height[i];
+        max_stages = std::max(max_stages, stages_of(b->height[i]));
+    }
+    b->sum_h = sum_h;
+    // the descriptors of every stage, one block: stage s serves the trees that reach level 9 s + 1
+    std::vector<MBatchTab> tabs;
+    std::vector<size_t> st_first(max_stages + 1), st_wgs(max_stages);
+    for (unsigned s = 0; s < max_stages; s++) {
+        st_first[s] = tabs.size();
+        size_t wg = 0;
+        for (size_t i = 0; i < k; i++) {
+            if (s >= stages_of(b->height[i])) continue;
+            const size_t n_in = b->npad[i] >> (s * MB_STAGE_LEVELS);
+            MBatchTab t{};
+            t.n = ns[i];
+            t.npad = b->npad[i];
+            t.lin = s * MB_STAGE_LEVELS;
+            t.height = b->height[i];
+            t.first_wg = (uint32_t)wg;
+            t.idx = (uint32_t)i;
+            tabs.push_back(t);
+            wg += (n_in + MB_BLOCK - 1) / MB_BLOCK;
+        }
+        if (wg >= ((size_t)1 << 31)) {
+            delete b;
+            return ZIGZ_ERR_TOO_MANY_VALUES;
+        }
+        st_wgs[s] = wg;
+    }
+    st_first[max_stages] = tabs.size();
+    b->desc_bytes = align256(std::max(tabs.size() * sizeof(MBatchTab), open_desc_bytes(k, sum_h)));
+    const size_t vals_bytes = align256(vw * 4 + 16), acc_bytes = align256(k * 8);
+    // pinned: roots | descriptors | (host form) values -- the last two go up in ONE copy, mirroring the device layout
+    const size_t roots_bytes = align256(k * 32);
+    const size_t up_bytes = b->desc_bytes + (values ? vw * 4 : 0);
+    uint8_t *pin;
+    zigz_status st = pinned(ctx, roots_bytes + up_bytes, &pin);
+    if (st != ZIGZ_OK) {
+        delete b;
+        return st;
+    }
+    uint8_t *h_roots = pin, *h_up = pin + roots_bytes;
+    if (values) {
+        const size_t bad = narrow_tables(values, ns, k, b->vals_off, (uint32_t *)(h_up + b->desc_bytes));
+        if (bad < k) {
+            delete b;
+            set_err(ctx, "table %zu contains a value >= p (not a canonical BabyBear element)", bad);
+            return fail_at(bad_index, bad, ZIGZ_ERR_NOT_CANONICAL);
+        }
+    }
+    if (hipMalloc(&b->d_mem, b->desc_bytes + vals_bytes + acc_bytes + nodes * 32) != hipSuccess) {
+        (void)hipGetLastError();
+        set_err(ctx, "hipMalloc of %zu bytes for a batch of %zu trees failed", b->desc_bytes + vals_bytes + acc_bytes + nodes * 32, k);
+        delete b;
+        return ZIGZ_ERR_OUT_OF_MEMORY;
+    }
+    b->d_desc = (uint8_t *)b->d_mem;
+    b->d_vals = (uint32_t *)(b->d_desc + b->desc_bytes);
+    b->d_acc = (unsigned long long *)((uint8_t *)b->d_vals + vals_bytes);
+    b->d_tree = (uint8_t *)b->d_acc + acc_bytes;
+    auto body = [&]() -> zigz_status {
+        for (auto &t : tabs) {
+            t.vals = b->d_vals + b->vals_off[t.idx];
+            t.src = values ? t.vals : d_values[t.idx];
+            t.tree = b->d_tree + b->tree_off[t.idx] * 32;
+        }
+        memcpy(h_up, tabs.data(), tabs.size() * sizeof(MBatchTab));
+        HIPCHK(ctx, hipMemcpyAsync(b->d_desc, h_up, up_bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(b->d_acc, 0, k * 8, ctx->stream));
+        const MBatchTab *d_tabs = (const MBatchTab *)b->d_desc;
+        launch_mbatch_subtrees(d_tabs, (unsigned)(st_first[1] - st_first[0]), (unsigned)st_wgs[0], ctx->stream);
+        for (unsigned s = 1; s < max_stages; s++)
+            launch_mbatch_level(d_tabs + st_first[s], (unsigned)(st_first[s + 1] - st_first[s]), (unsigned)st_wgs[s], ctx->stream);
+        const DoneFlag done = done_flag(ctx, 2);
+        launch_mbatch_roots(d_tabs, (unsigned)k, h_roots, ctx->stream, done);  // stage 0 holds every tree, in order
+        HIPCHK(ctx, hipGetLastError());
+        CHK(wait_done(ctx, done));
+        memcpy(roots, h_roots, k * 32);
+        if (heights)
+            for (size_t i = 0; i < k; i++) heights[i] = b->height[i];
+        return ZIGZ_OK;
+    };
+    st = body();
+    if (st != ZIGZ_OK || !out) {
+        batch_free(ctx, b);
+        return st;
+    }
+    *out = b;
+    return ZIGZ_OK;
+    ZIGZ_NOTHROW_END(ctx)
+}
+
+// the openings of every tree at idx[i]; points != nullptr: CommitmentScheme.open (the eval first, into the accumulators)
+zigz_status open_run(zigz_ctx *ctx, const zigz_merkle_batch *b, const uint64_t *idx, const uint64_t *points, uint64_t *values,
+                     uint8_t *siblings, uint8_t *dirs, uint64_t *leaf_values) {
+    const size_t k = b->k, sum_h = b->sum_h;
+    // pinned: siblings | dirs | leaves | values (written by the path launch) | descriptors + factors (one copy up)
+    const size_t sib_b = align256(sum_h * 32), dir_b = align256(sum_h), leaf_b = align256(k * 8), val_b = align256(k * 8);
+    const size_t out_bytes = sib_b + dir_b + leaf_b + val_b, up_bytes = open_desc_bytes(k, sum_h);
+    uint8_t *pin;
+    CHK(pinned(ctx, out_bytes + up_bytes, &pin));
+    MPathOut o;
+    o.sib = pin;
+    o.dirs = pin + sib_b;
+    o.leaf = (uint64_t *)(pin + sib_b + dir_b);
+    o.value = (uint64_t *)(pin + sib_b + dir_b + leaf_b);
+    uint8_t *h_up = pin + out_bytes;
+    MPathTab *hp = (MPathTab *)h_up;
+    MEvalTab *he = (MEvalTab *)(h_up + align256(k * sizeof(MPathTab)));
+    const size_t f_off = align256(k * sizeof(MPathTab)) + align256(k * sizeof(MEvalTab));
+    uint32_t *hf = (uint32_t *)(h_up + f_off);
+    const uint32_t *d_f = (const uint32_t *)(b->d_desc + f_off);
+    size_t wg = 0;
+    for (size_t i = 0; i < k; i++) {
+        MPathTab &p = hp[i];
+        p.vals = b->d_vals + b->vals_off[i];
+        p.tree = b->d_tree + b->tree_off[i] * 32;
+        p.acc = points ? b->d_acc + i : nullptr;
+        p.npad = b->npad[i];
+        p.index = idx[i];
+        p.sib_off = b->sib_off[i];
+        p.height = b->height[i];
+        p.idx = (uint32_t)i;
+        if (points) {
+            const unsigned nv = b->height[i];
+            const uint64_t *pt = points + b->sib_off[i];
+            for (unsigned v = 0; v < nv; v++) {  // eq factors of coordinate v (index bit v): 1 - r, r (Montgomery form)
+                hf[2 * (b->sib_off[i] + v)] = host_to_mont((1 + (uint64_t)P - pt[v]) % P);
+                hf[2 * (b->sib_off[i] + v) + 1] = host_to_mont(pt[v]);
+            }
+            MEvalTab &e = he[i];
+            e.vals = p.vals;
+            e.f = d_f + 2 * b->sib_off[i];
+            e.acc = b->d_acc + i;
+            e.n = b->n[i];
+            e.nv = nv;
+            e.first_wg = (uint32_t)wg;
+            wg += (b->n[i] + MB_EVAL_CHUNK - 1) / MB_EVAL_CHUNK;
+        }
+    }
+    HIPCHK(ctx, hipMemcpyAsync(b->d_desc, h_up, points ? up_bytes : k * sizeof(MPathTab), hipMemcpyHostToDevice, ctx->stream));
+    if (points) launch_mbatch_eval((const MEvalTab *)(b->d_desc + align256(k * sizeof(MPathTab))), (unsigned)k, (unsigned)wg, ctx->stream);
+    const DoneFlag done = done_flag(ctx, 2);
+    launch_mbatch_paths((const MPathTab *)b->d_desc, (unsigned)k, o, ctx->stream, done);
+    HIPCHK(ctx, hipGetLastError());
+    CHK(wait_done(ctx, done));
+    if (sum_h) {
+        memcpy(siblings, o.sib, sum_h * 32);
+        memcpy(dirs, o.dirs, sum_h);
+    }
+    memcpy(leaf_values, o.leaf, k * 8);
+    if (points) memcpy(values, o.value, k * 8);
+    return ZIGZ_OK;
+}
+
+}  // namespace
+
+extern "C" zigz_status zigz_dev_merkle_commit_batch(zigz_ctx *ctx, const uint32_t *const *d_values, const size_t *ns, size_t k,
+                                                    uint8_t *roots, size_t *heights, zigz_merkle_batch **out, size_t *bad_index) {
+    ZIGZ_ENTER(ctx);
+    if (!ctx) return ZIGZ_ERR_INVALID_ARGUMENT;
+    if (k == 0) return ZIGZ_OK;
+    if (k > ZIGZ_BATCH_MAX || !d_values || !ns || !roots) return ZIGZ_ERR_INVALID_ARGUMENT;
+    for (size_t i = 0; i < k; i++) {
+        const zigz_status st = table_pre(ns[i], d_values[i], true);
+        if (st != ZIGZ_OK) return fail_at(bad_index, i, st);
+    }
+    return commit_run(ctx, d_values, nullptr, ns, k, roots, heights, out, bad_index);
+}
+
+extern "C" zigz_status zigz_merkle_commit_batch(zigz_ctx *ctx, const uint64_t *const *values, const size_t *ns, size_t k,
+                                                uint8_t *roots, size_t *heights, zigz_merkle_batch **out, size_t *bad_index) {
+    ZIGZ_ENTER(ctx);
+    if (!ctx) return ZIGZ_ERR_INVALID_ARGUMENT;
+    if (k == 0) return ZIGZ_OK;
+    if (k > ZIGZ_BATCH_MAX || !values || !ns || !roots) return ZIGZ_ERR_INVALID_ARGUMENT;
+    ZIGZ_NOTHROW_BEGIN
+    size_t f = k;
+    zigz_status fst = ZIGZ_OK;
+    for (size_t i = 0; i < k && f == k; i++) {
+        const zigz_status st = table_pre(ns[i], values[i], false);
+        if (st != ZIGZ_OK) { f = i; fst = st; }
+    }
+    if (f < k) {  // a table before the first failing one may hold a value >= p: the single calls would stop there first
+        for (size_t i = 0; i < f; i++)
+            for (size_t j = 0; j < ns[i]; j++)
+                if (values[i][j] >= P) return fail_at(bad_index, i, ZIGZ_ERR_NOT_CANONICAL);
+        return fail_at(bad_index, f, fst);
+    }
+    return commit_run(ctx, nullptr, values, ns, k, roots, heights, out, bad_index);  // (checks the values while it narrows them)
+    ZIGZ_NOTHROW_END(ctx)
+}
+
+extern "C" zigz_status zigz_merkle_open_batch(zigz_ctx *ctx, const zigz_merkle_batch *b, const uint64_t *indices, uint8_t *siblings,
+                                              uint8_t *dirs, uint64_t *leaf_values, size_t *bad_index) {
+    ZIGZ_ENTER(ctx);
+    if (!ctx || !b || b->ctx != ctx || !indices || !leaf_values || (b->sum_h && (!siblings || !dirs))) return ZIGZ_ERR_INVALID_ARGUMENT;
+    for (size_t i = 0; i < b->k; i++)
+        if (indices[i] >= b->n[i]) return fail_at(bad_index, i, ZIGZ_ERR_INDEX_OUT_OF_BOUNDS);  // merkle_tree.zig:325
+    ZIGZ_NOTHROW_BEGIN
+    return open_run(ctx, b, indices, nullptr, nullptr, siblings, dirs, leaf_values);
+    ZIGZ_NOTHROW_END(ctx)
+}
+
+extern "C" zigz_status zigz_commit_open_batch(zigz_ctx *ctx, const zigz_merkle_batch *b, const uint64_t *points, uint64_t *values,
+                                              uint64_t *indices, uint8_t *siblings, uint8_t *dirs, uint64_t *leaf_values,
+                                              size_t *bad_index) {
+    ZIGZ_ENTER(ctx);
+    if (!ctx || !b || b->ctx != ctx || !values || !indices || !leaf_values || (b->sum_h && (!points || !siblings || !dirs)))
+        return ZIGZ_ERR_INVALID_ARGUMENT;
+    ZIGZ_NOTHROW_BEGIN
+    std::vector<uint64_t> idx(b->k);
+    for (size_t i = 0; i < b->k; i++) {
+        const zigz_status st = mle_check(b->n[i]);  // polynomial_commit.zig:86 (Multilinear.init)
+        if (st != ZIGZ_OK) return fail_at(bad_index, i, st);
+        const unsigned nv = b->height[i];
+        const uint64_t *pt = points + b->sib_off[i];
+        for (unsigned v = 0; v < nv; v++)
+            if (pt[v] >= P) return fail_at(bad_index, i, ZIGZ_ERR_NOT_CANONICAL);
+        idx[i] = nv == 0 ? 0 : pt[0] % ((uint64_t)1 << nv);  // pointToIndex, :178-183
+    }
+    CHK(open_run(ctx, b, idx.data(), points, values, siblings, dirs, leaf_values));
+    memcpy(indices, idx.data(), b->k * 8);
+    return ZIGZ_OK;
+    ZIGZ_NOTHROW_END(ctx)
+}
+
+extern "C" void zigz_merkle_batch_destroy(zigz_ctx *ctx, zigz_merkle_batch *b) {
+    ZIGZ_ENTER(ctx);
+    batch_free(ctx ? ctx : (b ? b->ctx : nullptr), b);
+}

@@ -186,6 +186,75 @@ bool CommitmentScheme::verify(const Hash &commitment, size_t num_vars, const Pol
     return SimpleMerkleTree::verify(commitment, proof.merkle_proof);
 }
 
+MerkleBatchTrees &MerkleBatchTrees::operator=(MerkleBatchTrees &&o) noexcept {
+    if (this != &o) {
+        if (b_) zigz_merkle_batch_destroy(ctx_, b_);
+        ctx_ = o.ctx_;
+        b_ = o.b_;
+        o.b_ = nullptr;
+    }
+    return *this;
+}
+MerkleBatchTrees::~MerkleBatchTrees() {
+    if (b_) zigz_merkle_batch_destroy(ctx_, b_);
+}
+CommitmentScheme::BatchCommit CommitmentScheme::batchCommit(const std::vector<Multilinear> &polys) {
+    zigz_ctx *ctx = polys.empty() ? nullptr : polys[0].ctx;
+    const size_t k = polys.size();
+    std::vector<const uint64_t *> vals(k);
+    std::vector<size_t> ns(k), heights(k);
+    for (size_t i = 0; i < k; i++) {
+        vals[i] = polys[i].evaluations.data();
+        ns[i] = polys[i].evaluations.size();
+    }
+    std::vector<uint8_t> roots(k * 32);
+    zigz_merkle_batch *b = nullptr;
+    if (k) check(ctx, zigz_merkle_commit_batch(ctx, vals.data(), ns.data(), k, roots.data(), heights.data(), &b, nullptr));
+    BatchCommit c{std::vector<PolyCommitment>(k), MerkleBatchTrees(ctx, b)};
+    for (size_t i = 0; i < k; i++) {
+        memcpy(c.commitments[i].commitment.data(), roots.data() + 32 * i, 32);
+        c.commitments[i].num_vars = polys[i].num_vars;
+    }
+    return c;
+}
+std::vector<PolyOpeningProof> CommitmentScheme::batchOpen(zigz_ctx *ctx, const BatchCommit &c,
+                                                          const std::vector<std::vector<F>> &points) {
+    const size_t k = c.commitments.size();
+    if (points.size() != k) check(ctx, ZIGZ_ERR_INVALID_ARGUMENT);
+    std::vector<PolyOpeningProof> out(k);
+    if (k == 0) return out;
+    std::vector<F> pts;
+    size_t sum_h = 0;
+    for (size_t i = 0; i < k; i++) {
+        if (points[i].size() != c.commitments[i].num_vars) check(ctx, ZIGZ_ERR_POINT_DIMENSION_MISMATCH);  // :92-94
+        pts.insert(pts.end(), points[i].begin(), points[i].end());
+        sum_h += points[i].size();
+    }
+    std::vector<uint64_t> values(k), indices(k), leaves(k);
+    std::vector<uint8_t> sib(sum_h * 32 + 1), dirs(sum_h + 1);
+    check(ctx, zigz_commit_open_batch(ctx, c.trees.handle(), pts.data(), values.data(), indices.data(), sib.data(), dirs.data(),
+                                      leaves.data(), nullptr));
+    for (size_t i = 0, o = 0; i < k; i++) {
+        PolyOpeningProof &p = out[i];
+        const size_t h = points[i].size();
+        p.point = points[i];
+        p.value = values[i];
+        p.merkle_proof.index = indices[i];
+        p.merkle_proof.value = leaves[i];
+        p.merkle_proof.path.siblings.resize(h);
+        p.merkle_proof.path.directions.assign(dirs.begin() + o, dirs.begin() + o + h);
+        for (size_t l = 0; l < h; l++) memcpy(p.merkle_proof.path.siblings[l].data(), sib.data() + 32 * (o + l), 32);
+        o += h;
+    }
+    return out;
+}
+bool CommitmentScheme::batchVerify(const std::vector<PolyCommitment> &commitments, const std::vector<PolyOpeningProof> &proofs) {
+    if (commitments.size() != proofs.size()) return false;  // :164-166
+    for (size_t i = 0; i < commitments.size(); i++)
+        if (!verify(commitments[i].commitment, commitments[i].num_vars, proofs[i])) return false;
+    return true;
+}
+
 // ---------------------------------------------------------------- Lasso
 static DenseTable build_table(int kind, size_t bits) {
     DenseTable t;

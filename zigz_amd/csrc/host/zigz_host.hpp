@@ -123,11 +123,34 @@ struct PolyOpeningProof {  // polynomial_commit.zig:42-55 OpeningProof(F)
     F value = 0;
     MerkleOpening merkle_proof;
 };
+struct PolyCommitment {  // polynomial_commit.zig:22-39
+    Hash commitment{};
+    size_t num_vars = 0;
+};
+class MerkleBatchTrees {  // the k trees of one batchCommit: ONE device allocation (zigz_merkle_batch)
+  public:
+    MerkleBatchTrees(zigz_ctx *ctx, zigz_merkle_batch *b) : ctx_(ctx), b_(b) {}
+    MerkleBatchTrees(MerkleBatchTrees &&o) noexcept : ctx_(o.ctx_), b_(o.b_) { o.b_ = nullptr; }
+    MerkleBatchTrees &operator=(MerkleBatchTrees &&o) noexcept;
+    ~MerkleBatchTrees();
+    zigz_merkle_batch *handle() const { return b_; }
+
+  private:
+    zigz_ctx *ctx_;
+    zigz_merkle_batch *b_;
+};
 struct CommitmentScheme {  // polynomial_commit.zig:58-185 (CommitmentSchemeSHA3)
     struct Commit { Hash commitment; size_t num_vars; SimpleMerkleTree tree; };
     static Commit commit(const Multilinear &poly);
     static PolyOpeningProof open(const Multilinear &poly, const SimpleMerkleTree &tree, const std::vector<F> &point);
     static bool verify(const Hash &commitment, size_t num_vars, const PolyOpeningProof &proof);
+    // batchCommit, :132-157: one zigz_merkle_commit_batch call for all polys (on polys[0]'s context)
+    struct BatchCommit { std::vector<PolyCommitment> commitments; MerkleBatchTrees trees; };
+    static BatchCommit batchCommit(const std::vector<Multilinear> &polys);
+    // open(polys[i], trees[i], points[i]) for every poly: one zigz_commit_open_batch call
+    static std::vector<PolyOpeningProof> batchOpen(zigz_ctx *ctx, const BatchCommit &c, const std::vector<std::vector<F>> &points);
+    // batchVerify, :160-175 (host SHA3, verifier side)
+    static bool batchVerify(const std::vector<PolyCommitment> &commitments, const std::vector<PolyOpeningProof> &proofs);
 };
 
 // ---------------------------------------------------------------- Lasso (src/lookups/)

@@ -1042,36 +1042,7 @@ void launch_keccak_small_l01(const uint32_t *d_vals, size_t val_stride, size_t n
 }
 
 // ------------------------------------------------------------------ K7: authentication paths
-// The last workgroup of a launch that wrote its results into pinned host memory says so there: every workgroup makes its
-// stores visible system-wide, then counts itself; the one that completes the count stores the sequence number the host polls
-// for (and leaves the counter at zero for the next launch).  A workgroup here is one wave.
-__device__ __forceinline__ void signal_done(const DoneFlag &done, unsigned n_groups) {
-    if (!done.flag) return;
-    __threadfence_system();
-    if (threadIdx.x == 0) {
-        const unsigned prev = atomicAdd(done.count, 1u);
-        if (prev == n_groups - 1) {
-            *done.count = 0;
-            __hip_atomic_store(done.flag, done.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-}
-// The same for workgroups of several waves: thread 0 may count its workgroup only once every wave has fenced its stores, so
-// a barrier sits between the fences and the count (without it the host could see the completion word while another wave's
-// words are still on their way).  Every thread of the workgroup must call it.
-__device__ __forceinline__ void signal_done_block(const DoneFlag &done, unsigned n_groups) {
-    if (!done.flag) return;
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned prev = atomicAdd(done.count, 1u);
-        if (prev == n_groups - 1) {
-            *done.count = 0;
-            __hip_atomic_store(done.flag, done.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-}
-
+// (completion flags of launches that publish into pinned host memory: signal_done / signal_done_block, tree_dev.hpp)
 __global__ __launch_bounds__(64) void k_paths(TreeRef t, size_t n_values, unsigned height, const uint32_t *__restrict__ vals,
                                               size_t val_stride, const uint64_t *__restrict__ idx, uint8_t *__restrict__ sib,
                                               uint8_t *__restrict__ dirs, uint32_t *__restrict__ leaf, DoneFlag done) {

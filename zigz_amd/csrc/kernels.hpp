@@ -453,4 +453,47 @@ struct FpTab {
 };
 void launch_batch_fingerprints(const FpTab *d_tabs, unsigned nt, unsigned nwg, hipStream_t s);
 
+// ---- batched Merkle trees (merkle_batch.hip): k independent dense trees of any sizes, each in the node layout of
+// slab_tree_ref (level l at node 2 npad - 2 (npad >> l)).  A build runs in stages of MB_STAGE_LEVELS levels: stage s reads
+// level 9 s (stage 0: the values, hashed into level 0) in blocks of up to MB_BLOCK nodes, one block per workgroup, and
+// computes the levels above each block in LDS -- so a batch takes ceil(height / 9) launches for its highest tree, whatever k is.
+constexpr unsigned MB_BLOCK = 512;
+constexpr unsigned MB_STAGE_LEVELS = 9;  // log2(MB_BLOCK)
+constexpr unsigned MB_EVAL_CHUNK = 4096;  // values per workgroup of the batched eval
+struct MBatchTab {  // one tree in one stage; the workgroups of tree j are [first_wg, first_wg of tree j + 1)
+    const uint32_t *src;  // stage 0: the values to hash (the caller's device table, or the handle's own copy)
+    uint32_t *vals;       // the handle's copy of the values: stage 0 writes it when src != vals
+    uint8_t *tree;        // 2 npad nodes
+    uint64_t n, npad;
+    uint32_t lin;         // the level this stage reads (0 for stage 0: the leaves it hashes)
+    uint32_t height;
+    uint32_t first_wg;
+    uint32_t idx;         // the tree's position in the batch
+    uint64_t reserved;
+};
+struct MPathTab {  // one opening: tree.open(index) (and the eval computed into *acc before, if acc != nullptr)
+    const uint32_t *vals;
+    const uint8_t *tree;
+    unsigned long long *acc;  // the batched eval's exact sum (left zero), or nullptr
+    uint64_t npad, index;
+    uint64_t sib_off;         // siblings at h_sib + 32 sib_off, directions at h_dirs + sib_off
+    uint32_t height, idx;
+};
+struct MEvalTab {  // eval(point) of one power-of-two table: sum_i T[i] prod_v f[2 v + bit v of i]  (exact, into *acc)
+    const uint32_t *vals;
+    const uint32_t *f;        // 2 nv Montgomery-form factors: (1 - r_v), r_v
+    unsigned long long *acc;
+    uint64_t n;
+    uint32_t nv, first_wg;
+};
+struct MPathOut {  // where the openings go (pinned host memory)
+    uint8_t *sib, *dirs;
+    uint64_t *leaf, *value;
+};
+void launch_mbatch_subtrees(const MBatchTab *d_tabs, unsigned nt, unsigned nwg, hipStream_t s);
+void launch_mbatch_level(const MBatchTab *d_tabs, unsigned nt, unsigned nwg, hipStream_t s);
+void launch_mbatch_roots(const MBatchTab *d_tabs, unsigned nt, uint8_t *h_roots, hipStream_t s, DoneFlag done);
+void launch_mbatch_eval(const MEvalTab *d_tabs, unsigned nt, unsigned nwg, hipStream_t s);
+void launch_mbatch_paths(const MPathTab *d_tabs, unsigned nt, const MPathOut &out, hipStream_t s, DoneFlag done);
+
 }  // namespace zk

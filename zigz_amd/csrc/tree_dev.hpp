@@ -1,5 +1,6 @@
-// Device-side helpers shared by the translation units that build Merkle trees (kernels.hip, merkle_levels.hip): the
-// workgroup size, digest loads / stores in the kernels' tree form (keccak.hpp), the timed-launch macro.
+// Device-side helpers shared by the translation units that build Merkle trees (kernels.hip, merkle_levels.hip,
+// merkle_batch.hip): the workgroup size, digest loads / stores in the kernels' tree form (keccak.hpp), the timed-launch macro,
+// the completion flags of launches that publish into pinned memory.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -137,6 +138,37 @@ __device__ __forceinline__ Digest load_digest_at(const uint8_t *p) {
 __device__ __forceinline__ void store_digest_at(uint8_t *p, const Digest &d) {
     unsigned long long *q = reinterpret_cast<unsigned long long *>(p);
     q[0] = d.w[0]; q[1] = d.w[1]; q[2] = d.w[2]; q[3] = d.w[3];
+}
+
+// ---- completion of a launch that publishes into pinned host memory (DoneFlag, kernels.hpp)
+// The last workgroup of a launch that wrote its results into pinned host memory says so there: every workgroup makes its
+// stores visible system-wide, then counts itself; the one that completes the count stores the sequence number the host polls
+// for (and leaves the counter at zero for the next launch).  A workgroup here is one wave.
+__device__ __forceinline__ void signal_done(const DoneFlag &done, unsigned n_groups) {
+    if (!done.flag) return;
+    __threadfence_system();
+    if (threadIdx.x == 0) {
+        const unsigned prev = atomicAdd(done.count, 1u);
+        if (prev == n_groups - 1) {
+            *done.count = 0;
+            __hip_atomic_store(done.flag, done.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+// The same for workgroups of several waves: thread 0 may count its workgroup only once every wave has fenced its stores, so
+// a barrier sits between the fences and the count (without it the host could see the completion word while another wave's
+// words are still on their way).  Every thread of the workgroup must call it.
+__device__ __forceinline__ void signal_done_block(const DoneFlag &done, unsigned n_groups) {
+    if (!done.flag) return;
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned prev = atomicAdd(done.count, 1u);
+        if (prev == n_groups - 1) {
+            *done.count = 0;
+            __hip_atomic_store(done.flag, done.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
 }
 
 }  // namespace zk

@@ -410,6 +410,56 @@ class Context:
         self.check_batch(lib.zigz_dev_sumcheck_prove_batch(self.h, ptrs, nsa, k, cp, rp, ptp, fep, C.byref(bad)), bad)
         return self._batch_split(nvs, r, pt, fe)
 
+    def _merkle_batch_out(self, rc, bad, k, roots, heights, handle, ns, keep):
+        self.check_batch(rc, bad)
+        res = [(roots[32 * i: 32 * (i + 1)].tobytes(), int(heights[i])) for i in range(k)]
+        return res, (MerkleBatch(self, handle, ns, [h for _, h in res]) if keep and k else None)
+
+    def merkle_commit_batch(self, tables, keep=True):
+        """zigz_merkle_commit_batch: SimpleMerkleTree.build(t) for every table (any lengths), in shared launches
+        (CommitmentScheme.batchCommit).  Returns ([(root, height)], MerkleBatch or None when keep is False)."""
+        k = len(tables)
+        arrs = [_u64(t) for t in tables]
+        ns = (C.c_size_t * max(k, 1))(*[len(t) for t in tables])
+        ptrs = (u64p * max(k, 1))(*[p for _, p in arrs])
+        roots, rp = _out_u8(32 * k)
+        heights = (C.c_size_t * max(k, 1))()
+        h, bad = vp(), C.c_size_t(0)
+        rc = lib.zigz_merkle_commit_batch(self.h, ptrs, ns, k, rp, heights, C.byref(h) if keep else None, C.byref(bad))
+        return self._merkle_batch_out(rc, bad, k, roots, heights, h, [len(t) for t in tables], keep)
+
+    def dev_merkle_commit_batch(self, d_tables, ns, keep=True):
+        """zigz_dev_merkle_commit_batch over device-resident tables (packed u32 canonical, 4-byte aligned)."""
+        k = len(ns)
+        nsa = (C.c_size_t * max(k, 1))(*[int(n) for n in ns])
+        ptrs = (vp * max(k, 1))(*[int(d) for d in d_tables])
+        roots, rp = _out_u8(32 * k)
+        heights = (C.c_size_t * max(k, 1))()
+        h, bad = vp(), C.c_size_t(0)
+        rc = lib.zigz_dev_merkle_commit_batch(self.h, ptrs, nsa, k, rp, heights, C.byref(h) if keep else None, C.byref(bad))
+        return self._merkle_batch_out(rc, bad, k, roots, heights, h, [int(n) for n in ns], keep)
+
+    def commit_open_batch(self, batch, points):
+        """zigz_commit_open_batch: CommitmentScheme.open(poly_i, tree_i, points[i]) for every table of the batch (each table
+        2^v values, points[i] of v coordinates).  Returns per-table dicts like CommitmentScheme.open."""
+        k, tot = len(batch.heights), sum(batch.heights)
+        if len(points) != k or any(len(p) != h for p, h in zip(points, batch.heights)):
+            raise ValueError("points[i] must have heights[i] coordinates, one point per table")
+        q, qp = _u64(np.concatenate([np.asarray(x, dtype=np.uint64).reshape(-1) for x in points] + [np.zeros(1, np.uint64)]))
+        vals, vlp = _out_u64(k)
+        idx, ip = _out_u64(k)
+        leaf, lp = _out_u64(k)
+        sib, sp = _out_u8(32 * tot)
+        dirs, dp = _out_u8(tot)
+        bad = C.c_size_t(0)
+        self.check_batch(lib.zigz_commit_open_batch(self.h, batch.h, qp, vlp, ip, sp, dp, lp, C.byref(bad)), bad)
+        out, o = [], 0
+        for i, v in enumerate(batch.heights):
+            out.append(dict(value=int(vals[i]), index=int(idx[i]), leaf=int(leaf[i]), siblings=sib[32 * o: 32 * (o + v)].tobytes(),
+                            directions=dirs[o: o + v].tobytes()))
+            o += v
+        return out
+
     def lasso_prove_batch(self, instances):
         """zigz_lasso_prove_batch: instances are dicts with table, queries and optional n_in (2), n_out (1), mapping (None).
         Returns the list of lasso_prove() dicts."""
@@ -524,6 +574,43 @@ class SimpleMerkleTree:
         if self.t:
             lib.zigz_merkle_destroy(self.ctx.h, self.t)
             self.t = None
+
+    def __del__(self):
+        try:
+            self.deinit()
+        except Exception:
+            pass
+
+
+class MerkleBatch:
+    """The trees of one zigz_merkle_commit_batch call (Context.merkle_commit_batch): values and trees of all tables in one
+    device allocation."""
+
+    def __init__(self, ctx, h, ns, heights):
+        self.ctx, self.h, self.ns, self.heights = ctx, h, list(ns), list(heights)
+
+    def open(self, indices):
+        """zigz_merkle_open_batch: tree_i.open(indices[i]) for every tree; per-tree dicts like SimpleMerkleTree.open"""
+        k, tot = len(self.heights), sum(self.heights)
+        ix, ixp = _u64(np.asarray(indices, dtype=np.uint64).reshape(-1))
+        if len(indices) != k:
+            raise ValueError(f"{len(indices)} indices for {k} trees")
+        leaf, lp = _out_u64(k)
+        sib, sp = _out_u8(32 * tot)
+        dirs, dp = _out_u8(tot)
+        bad = C.c_size_t(0)
+        self.ctx.check_batch(lib.zigz_merkle_open_batch(self.ctx.h, self.h, ixp, sp, dp, lp, C.byref(bad)), bad)
+        out, o = [], 0
+        for i, v in enumerate(self.heights):
+            out.append(dict(index=int(ix[i]), value=int(leaf[i]), siblings=sib[32 * o: 32 * (o + v)].tobytes(),
+                            directions=dirs[o: o + v].tobytes()))
+            o += v
+        return out
+
+    def deinit(self):
+        if self.h:
+            lib.zigz_merkle_batch_destroy(self.ctx.h, self.h)
+            self.h = None
 
     def __del__(self):
         try:

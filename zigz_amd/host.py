@@ -57,6 +57,7 @@ SIGNATURES = {
     "zigzh_lasso_prove_table": (C.c_int, [vp, C.c_int, C.c_size_t, u64p, C.c_size_t, u64p, C.c_size_t, u8p, szp, u8p,
                                           u8p, szp]),
     "zigzh_commit_open_verify": (C.c_int, [vp, u64p, C.c_size_t, u64p, C.c_size_t, u8p, u64p, u64p, C.POINTER(C.c_int)]),
+    "zigzh_batch_verify": (C.c_int, [u8p, szp, C.c_size_t, u64p, u64p, u64p, u64p, u8p, u8p, C.POINTER(C.c_int)]),
 }
 for _n, (_r, _a) in SIGNATURES.items():
     _f = getattr(lib, _n)
@@ -89,6 +90,30 @@ def _take(ptr, n):
         return C.string_at(ptr, n.value)
     finally:
         lib.zigzh_free(ptr)
+
+
+def batch_verify(commitments, proofs):
+    """CommitmentScheme.batchVerify (polynomial_commit.zig:160-175) on the host: commitments are (root, num_vars) pairs, proofs
+    dicts with point, value, index, leaf, siblings (32 B each) and directions -- the form Context.commit_open_batch returns,
+    plus the point."""
+    k = len(commitments)
+    if k != len(proofs):
+        return False
+    roots = np.frombuffer(b"".join(bytes(r) for r, _ in commitments) or b"\0", dtype=np.uint8).copy()
+    nv = (C.c_size_t * max(k, 1))(*[int(v) for _, v in commitments])
+    pts, pp = _u64(np.concatenate([np.asarray(p["point"], dtype=np.uint64).reshape(-1) for p in proofs] + [np.zeros(0, np.uint64)]))
+    vals, vlp = _u64([p["value"] for p in proofs])
+    idx, ip = _u64([p["index"] for p in proofs])
+    leaf, lp = _u64([p["leaf"] for p in proofs])
+    sib = np.frombuffer(b"".join(p["siblings"] for p in proofs) + b"\0", dtype=np.uint8).copy()
+    dirs = np.frombuffer(b"".join(p["directions"] for p in proofs) + b"\0", dtype=np.uint8).copy()
+    for (_, v), p in zip(commitments, proofs):  # the C arrays are laid out by num_vars: a proof of another length is rejected
+        if len(p["point"]) != v or len(p["siblings"]) != 32 * v or len(p["directions"]) != v:
+            return False
+    ok = C.c_int(0)
+    _check(lib.zigzh_batch_verify(roots.ctypes.data_as(u8p), nv, k, pp, vlp, ip, lp, sib.ctypes.data_as(u8p),
+                                  dirs.ctypes.data_as(u8p), C.byref(ok)))
+    return bool(ok.value)
 
 
 TIMING_NAMES = ["commit_begin", "sumcheck_transcript", "lasso_transcript", "wait_roots", "roots_challenges", "open_all",
