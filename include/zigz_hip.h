@@ -492,6 +492,27 @@ zigz_status zigz_commit_open_batch(zigz_ctx *ctx, const zigz_merkle_batch *b, co
                                    size_t *bad_index);
 /* waits for the context's stream, then frees the batch (NULL: no-op) */
 void zigz_merkle_batch_destroy(zigz_ctx *ctx, zigz_merkle_batch *b);
+/* SimpleMerkleTree.verify (merkle_tree.zig:362-373) for k independent openings in shared launches; CommitmentScheme.batchVerify
+ * (polynomial_commit.zig:160-175) is "*n_rejected == 0".  Opening i: roots[32 i..], heights[i] levels, leaf_values[i] (hashed as
+ * its 8 little-endian bytes, like hashLeaf: values >= p are hashed as given), siblings (32 B each) and dirs packed opening by
+ * opening at offset sum_{j<i} heights[j] (the layout zigz_merkle_open_batch / zigz_commit_open_batch write).  dirs[l] != 0:
+ * the sibling is on the left (is_right).  Height 0: the check is hashLeaf(value) == root.  verdicts (k bytes, may be NULL):
+ * 1 accept, 0 reject, bit for bit SimpleMerkleTree.verify; *n_rejected: the number of zeros.  What an opening holds never makes
+ * an error: statuses are for the shape of the arguments only -- ZIGZ_ERR_INVALID_ARGUMENT for ctx or n_rejected NULL, a NULL
+ * array when k > 0, k > ZIGZ_VERIFY_BATCH_MAX, or heights[i] > 64 (the first such i goes to *bad_index, if non-NULL), all
+ * checked before anything runs.  k == 0: ZIGZ_OK, *n_rejected = 0, nothing else touched.  The call queues on the context's
+ * stream and leaves the hint options, zigz_kernel_stats, an active commit job and open zigz_merkle_batch handles alone.
+ * Host form: staged in chunks of at most 32 MiB through pinned memory (each bucket of one height level-major). */
+#define ZIGZ_VERIFY_BATCH_MAX 4194304 /* 2^22 */
+zigz_status zigz_merkle_verify_batch(zigz_ctx *ctx, size_t k, const uint8_t *roots, const size_t *heights,
+                                     const uint64_t *leaf_values, const uint8_t *siblings, const uint8_t *dirs,
+                                     uint8_t *verdicts, size_t *n_rejected, size_t *bad_index);
+/* the same over device-resident roots / leaf_values / siblings / dirs (same layouts; d_roots and d_siblings 16-byte aligned,
+ * d_leaf_values 8-byte aligned, else ZIGZ_ERR_INVALID_ARGUMENT); heights and the outputs stay on the host.  Option
+ * "verify_pause" (A/B): 0 = hash with the re-arm pauses in launches of >= 4096 waves (default), 1 = always, 2 = never. */
+zigz_status zigz_dev_merkle_verify_batch(zigz_ctx *ctx, size_t k, const uint8_t *d_roots, const size_t *heights,
+                                         const uint64_t *d_leaf_values, const uint8_t *d_siblings, const uint8_t *d_dirs,
+                                         uint8_t *verdicts, size_t *n_rejected, size_t *bad_index);
 
 /* ---------------------------------------------------------------- host SHA3 sponge / transcript
  * FiatShamirTranscript   src/core/hash.zig:255-324 (sequential by construction: stays on the host) */

@@ -192,6 +192,8 @@ extern "C" void zigz_ctx_destroy(zigz_ctx *ctx) {
     for (int i = 0; i < 2 * KEV_MAX; i++)
         if (ctx->kev[i]) (void)hipEventDestroy(ctx->kev[i]);
     if (ctx->epoch_own) (void)hipEventDestroy(ctx->epoch_own);
+    for (int i = 0; i < 2; i++)
+        if (ctx->ev_verify[i]) (void)hipEventDestroy(ctx->ev_verify[i]);
     if (ctx->d_flush) (void)hipFree(ctx->d_flush);
     if (ctx->d_sd_tables) (void)hipFree(ctx->d_sd_tables);
     if (ctx->d_sd_fallbacks) (void)hipFree(ctx->d_sd_fallbacks);
@@ -294,6 +296,7 @@ extern "C" zigz_status zigz_ctx_set_option(zigz_ctx *ctx, const char *name, int6
     if (strcmp(name, "cons_always") == 0) { ctx->cons_always = value != 0; return ZIGZ_OK; }
     if (strcmp(name, "debug_skip") == 0) { ctx->debug_skip = (int)value; return ZIGZ_OK; }
     if (strcmp(name, "small_domain_mask") == 0) { ctx->small_domain_mask = (uint64_t)value; return ZIGZ_OK; }
+    if (strcmp(name, "verify_pause") == 0) { ctx->verify_pause = value == 1 ? 1 : value == 2 ? 2 : 0; return ZIGZ_OK; }
     if (strcmp(name, "batch_reserve") == 0) { ctx->batch_reserve = value < 0 ? 0 : value > BATCH_MAX ? BATCH_MAX : (unsigned)value; return ZIGZ_OK; }
     return ZIGZ_ERR_INVALID_ARGUMENT;
 }
@@ -306,6 +309,7 @@ extern "C" zigz_status zigz_ctx_get_option(zigz_ctx *ctx, const char *name, int6
     if (strcmp(name, "cons_group_mask") == 0) { *value = (int64_t)ctx->cons_group_mask; return ZIGZ_OK; }
     if (strcmp(name, "cons_always") == 0) { *value = ctx->cons_always; return ZIGZ_OK; }
     if (strcmp(name, "small_domain_mask") == 0) { *value = (int64_t)ctx->small_domain_mask; return ZIGZ_OK; }
+    if (strcmp(name, "verify_pause") == 0) { *value = ctx->verify_pause; return ZIGZ_OK; }
     return ZIGZ_ERR_INVALID_ARGUMENT;
 }
 extern "C" zigz_status zigz_ctx_set_epoch(zigz_ctx *ctx, zigz_ctx *owner) {

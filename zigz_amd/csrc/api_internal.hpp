@@ -24,7 +24,7 @@
 using namespace zk;
 
 // ------------------------------------------------------------------ context
-enum { WS_IN64 = 0, WS_IN32, WS_OUT32, WS_OUT64, WS_SCRATCH, WS_TREE, WS_FOLD, WS_MISC, WS_COLS, WS_LASSO, WS_DEDUP, WS_WITNESS, WS_RUNS, WS_RUNMETA, WS_CONS, WS_CONSMETA, WS_BATCH, WS_SCBATCH, WS_SCBATCH_IN, WS_SLOTS };
+enum { WS_IN64 = 0, WS_IN32, WS_OUT32, WS_OUT64, WS_SCRATCH, WS_TREE, WS_FOLD, WS_MISC, WS_COLS, WS_LASSO, WS_DEDUP, WS_WITNESS, WS_RUNS, WS_RUNMETA, WS_CONS, WS_CONSMETA, WS_BATCH, WS_SCBATCH, WS_SCBATCH_IN, WS_VERIFY, WS_SLOTS };
 
 constexpr int KEV_MAX = 72;
 struct ListCaps {
@@ -100,6 +100,8 @@ struct zigz_ctx {
                              // are allocated once and not again when a larger batch than any before comes along
     uint64_t *h_batch;        // pinned region of the batched provers (api_batch.cpp) when a batch outgrows h_pin; grown, never shrunk
     size_t h_batch_bytes;
+    hipEvent_t ev_verify[2];  // the batched verify's host form: the upload from each half of its pinned staging (created on first use)
+    int verify_pause;         // option "verify_pause": 0 = by launch size, 1 = always, 2 = never (A/B)
 };
 static const size_t FLUSH_BYTES = (size_t)1 << 30;
 static const size_t SUMS_SLOTS = 8192;  // [0, 4096): results of the API calls; [4096, 8192): scratch of the measurement hook

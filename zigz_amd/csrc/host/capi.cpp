@@ -577,28 +577,52 @@ extern "C" int zigzh_commit_open_verify(zigz_ctx *ctx, const uint64_t *evals, si
     });
 }
 
-// CommitmentScheme.batchVerify (polynomial_commit.zig:160-175) over k openings given as parallel arrays: num_vars[i] coordinates,
-// siblings and directions per proof, concatenated in proof order (the layout of zigz_commit_open_batch)
+// k openings given as parallel arrays: num_vars[i] coordinates, siblings and directions per proof, concatenated in proof order
+// (the layout of zigz_commit_open_batch)
+static void unpack_openings(const uint8_t *commitments, const size_t *num_vars, size_t k, const uint64_t *points,
+                            const uint64_t *values, const uint64_t *indices, const uint64_t *leaf_values, const uint8_t *siblings,
+                            const uint8_t *dirs, std::vector<PolyCommitment> &cs, std::vector<PolyOpeningProof> &ps) {
+    cs.resize(k);
+    ps.resize(k);
+    for (size_t i = 0, o = 0; i < k; i++) {
+        const size_t h = num_vars[i];
+        memcpy(cs[i].commitment.data(), commitments + 32 * i, 32);
+        cs[i].num_vars = h;
+        PolyOpeningProof &p = ps[i];
+        p.point.assign(points + o, points + o + h);
+        p.value = values[i];
+        p.merkle_proof.index = indices[i];
+        p.merkle_proof.value = leaf_values[i];
+        p.merkle_proof.path.siblings.resize(h);
+        p.merkle_proof.path.directions.assign(dirs + o, dirs + o + h);
+        for (size_t l = 0; l < h; l++) memcpy(p.merkle_proof.path.siblings[l].data(), siblings + 32 * (o + l), 32);
+        o += h;
+    }
+}
+
+// CommitmentScheme.batchVerify (polynomial_commit.zig:160-175) over k openings in the layout above
 extern "C" int zigzh_batch_verify(const uint8_t *commitments, const size_t *num_vars, size_t k, const uint64_t *points,
                                   const uint64_t *values, const uint64_t *indices, const uint64_t *leaf_values,
                                   const uint8_t *siblings, const uint8_t *dirs, int *ok) {
     return guard([&] {
-        std::vector<PolyCommitment> cs(k);
-        std::vector<PolyOpeningProof> ps(k);
-        for (size_t i = 0, o = 0; i < k; i++) {
-            const size_t h = num_vars[i];
-            memcpy(cs[i].commitment.data(), commitments + 32 * i, 32);
-            cs[i].num_vars = h;
-            PolyOpeningProof &p = ps[i];
-            p.point.assign(points + o, points + o + h);
-            p.value = values[i];
-            p.merkle_proof.index = indices[i];
-            p.merkle_proof.value = leaf_values[i];
-            p.merkle_proof.path.siblings.resize(h);
-            p.merkle_proof.path.directions.assign(dirs + o, dirs + o + h);
-            for (size_t l = 0; l < h; l++) memcpy(p.merkle_proof.path.siblings[l].data(), siblings + 32 * (o + l), 32);
-            o += h;
-        }
+        std::vector<PolyCommitment> cs;
+        std::vector<PolyOpeningProof> ps;
+        unpack_openings(commitments, num_vars, k, points, values, indices, leaf_values, siblings, dirs, cs, ps);
         *ok = CommitmentScheme::batchVerify(cs, ps) ? 1 : 0;
+    });
+}
+
+// the same on ctx's device (CommitmentScheme::batchVerify(ctx, ...)); verdicts (k bytes, may be NULL): 1 / 0 per proof
+extern "C" int zigzh_batch_verify_dev(zigz_ctx *ctx, const uint8_t *commitments, const size_t *num_vars, size_t k,
+                                      const uint64_t *points, const uint64_t *values, const uint64_t *indices,
+                                      const uint64_t *leaf_values, const uint8_t *siblings, const uint8_t *dirs, uint8_t *verdicts,
+                                      int *ok) {
+    return guard([&] {
+        std::vector<PolyCommitment> cs;
+        std::vector<PolyOpeningProof> ps;
+        unpack_openings(commitments, num_vars, k, points, values, indices, leaf_values, siblings, dirs, cs, ps);
+        std::vector<uint8_t> v;
+        *ok = CommitmentScheme::batchVerify(ctx, cs, ps, &v) ? 1 : 0;
+        if (verdicts && k) memcpy(verdicts, v.data(), k);
     });
 }

@@ -1,5 +1,6 @@
 // Transcript, Multilinear, sumcheck, Merkle, commitment scheme, Lasso: thin host objects whose
 // arithmetic is delegated to libzigz_hip.so.
+#include <algorithm>
 #include <cstring>
 
 #include "zigz_host.hpp"
@@ -253,6 +254,37 @@ bool CommitmentScheme::batchVerify(const std::vector<PolyCommitment> &commitment
     for (size_t i = 0; i < commitments.size(); i++)
         if (!verify(commitments[i].commitment, commitments[i].num_vars, proofs[i])) return false;
     return true;
+}
+bool CommitmentScheme::batchVerify(zigz_ctx *ctx, const std::vector<PolyCommitment> &commitments,
+                                   const std::vector<PolyOpeningProof> &proofs, std::vector<uint8_t> *verdicts) {
+    if (commitments.size() != proofs.size()) return false;  // :164-166
+    const size_t k = proofs.size();
+    std::vector<uint8_t> v(k, 0), roots, sib, dirs;
+    std::vector<size_t> heights, which;  // which: the openings that reach the Merkle check
+    std::vector<uint64_t> leaves;
+    for (size_t i = 0; i < k; i++) {
+        const MerklePath &path = proofs[i].merkle_proof.path;
+        if (proofs[i].point.size() != commitments[i].num_vars) continue;  // :123-125
+        if (path.directions.size() != path.siblings.size() || path.siblings.size() > 64) continue;
+        which.push_back(i);
+        roots.insert(roots.end(), commitments[i].commitment.begin(), commitments[i].commitment.end());
+        heights.push_back(path.siblings.size());
+        leaves.push_back(proofs[i].merkle_proof.value);
+        for (const Hash &h : path.siblings) sib.insert(sib.end(), h.begin(), h.end());
+        dirs.insert(dirs.end(), path.directions.begin(), path.directions.end());
+    }
+    sib.push_back(0);  // (non-NULL arrays when every path is empty)
+    dirs.push_back(0);
+    if (!which.empty()) {
+        std::vector<uint8_t> got(which.size());
+        size_t rejected = 0;
+        check(ctx, zigz_merkle_verify_batch(ctx, which.size(), roots.data(), heights.data(), leaves.data(), sib.data(), dirs.data(),
+                                            got.data(), &rejected, nullptr));
+        for (size_t w = 0; w < which.size(); w++) v[which[w]] = got[w];
+    }
+    const bool all = std::all_of(v.begin(), v.end(), [](uint8_t x) { return x == 1; });
+    if (verdicts) *verdicts = std::move(v);
+    return all;
 }
 
 // ---------------------------------------------------------------- Lasso

@@ -151,6 +151,11 @@ struct CommitmentScheme {  // polynomial_commit.zig:58-185 (CommitmentSchemeSHA3
     static std::vector<PolyOpeningProof> batchOpen(zigz_ctx *ctx, const BatchCommit &c, const std::vector<std::vector<F>> &points);
     // batchVerify, :160-175 (host SHA3, verifier side)
     static bool batchVerify(const std::vector<PolyCommitment> &commitments, const std::vector<PolyOpeningProof> &proofs);
+    // the same on ctx's device (zigz_merkle_verify_batch, one lane per opening): verify's rule per opening -- a point of another
+    // length than num_vars rejects that opening alone (:123-125), as does a path whose directions and siblings differ in
+    // number or that is higher than any tree (64); verdicts (if non-NULL) gets 1 / 0 per opening, in order
+    static bool batchVerify(zigz_ctx *ctx, const std::vector<PolyCommitment> &commitments, const std::vector<PolyOpeningProof> &proofs,
+                            std::vector<uint8_t> *verdicts = nullptr);
 };
 
 // ---------------------------------------------------------------- Lasso (src/lookups/)

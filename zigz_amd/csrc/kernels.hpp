@@ -496,4 +496,27 @@ void launch_mbatch_roots(const MBatchTab *d_tabs, unsigned nt, uint8_t *h_roots,
 void launch_mbatch_eval(const MEvalTab *d_tabs, unsigned nt, unsigned nwg, hipStream_t s);
 void launch_mbatch_paths(const MPathTab *d_tabs, unsigned nt, const MPathOut &out, hipStream_t s, DoneFlag done);
 
+// ---- batched Merkle verification (merkle_verify.hip): SimpleMerkleTree.verify for k independent openings, one lane per
+// opening.  The openings are sorted by height (a stable counting sort on the host); a bucket is a run of sorted positions of
+// one height and owns whole workgroups, so every wave walks the same number of levels.
+constexpr unsigned MV_TPB = 256;  // threads per workgroup of the verify launch (a bucket owns whole workgroups)
+struct MVerifyTab {  // one bucket: the workgroups of bucket j are [first_wg, first_wg of bucket j + 1)
+    const uint8_t *sib;   // host form: the bucket's siblings level-major (level l of lane i at 32 (l cnt + i)); device form: unused
+    const uint8_t *dirs;  // host form: the bucket's directions level-major (l cnt + i); device form: unused
+    uint64_t base;        // the bucket's first sorted position
+    uint32_t cnt, height, first_wg, pad;
+};
+struct MVerifyArgs {
+    const uint8_t *roots;        // 32 B per opening: host form in sorted order from position lo, device form in the caller's order
+    const uint64_t *vals;        // likewise
+    const uint8_t *sib, *dirs;   // device form: the caller's packed layout (opening i at soff of its sorted position)
+    const uint32_t *order;       // sorted position lo + n -> the caller's index, at order[n]
+    uint64_t lo;                 // host form: the first sorted position of the chunk the arrays hold (device form: 0)
+    const uint32_t *soff;        // device form: the caller's sibling offset of the opening at each sorted position
+    uint8_t *verdicts;           // pinned, the caller's order: 1 accept, 0 reject
+    unsigned long long *rejected;  // device counter: one atomic add per wave
+};
+// dev: the device form's gather; pause: sha3 with the re-arm pauses (keccak.hpp)
+void launch_mverify(const MVerifyTab *d_tabs, unsigned nt, unsigned nwg, const MVerifyArgs &a, bool dev, bool pause, hipStream_t s);
+
 }  // namespace zk

@@ -460,6 +460,55 @@ class Context:
             o += v
         return out
 
+    # ---- batched Merkle verification (one lane per opening)
+    def _verify_batch(self, fn, k, roots, heights, leaves, siblings, dirs):
+        hs = (C.c_size_t * max(k, 1))(*[int(h) for h in heights])
+        verd, vp_ = _out_u8(k)
+        rej, bad = C.c_size_t(0), C.c_size_t(0)
+        self.check_batch(fn(self.h, k, roots, hs, leaves, siblings, dirs, vp_, C.byref(rej), C.byref(bad)), bad)
+        return verd[:k].copy()
+
+    def merkle_verify_batch(self, roots, heights, leaves, siblings, dirs):
+        """zigz_merkle_verify_batch: SimpleMerkleTree.verify for k openings -- roots (k x 32 bytes), heights, leaf values (u64,
+        hashed as given), siblings (32 B each) and directions packed opening by opening.  Returns the np.uint8 verdicts."""
+        k = len(heights)
+        r = np.frombuffer(bytes(roots) + b"\0" * 32, dtype=np.uint8).copy()
+        if len(r) != 32 * k + 32:
+            raise ValueError(f"{len(r) - 32} root bytes for {k} openings")
+        lv, lp = _u64(np.asarray(leaves, dtype=np.uint64).reshape(-1))
+        sib = np.frombuffer(bytes(siblings) + b"\0" * 32, dtype=np.uint8).copy()
+        d = np.frombuffer(bytes(dirs) + b"\0", dtype=np.uint8).copy()
+        tot = sum(int(h) for h in heights)
+        if len(lv) < k or len(sib) != 32 * tot + 32 or len(d) != tot + 1:
+            raise ValueError("leaves, siblings and dirs must hold k values, 32 * sum(heights) and sum(heights) bytes")
+        return self._verify_batch(lib.zigz_merkle_verify_batch, k, r.ctypes.data_as(u8p), heights, lp, sib.ctypes.data_as(u8p),
+                                  d.ctypes.data_as(u8p))
+
+    def dev_merkle_verify_batch(self, d_roots, heights, d_leaves, d_siblings, d_dirs):
+        """zigz_dev_merkle_verify_batch over device-resident roots (16-byte aligned), leaf values (u64, 8-byte aligned),
+        siblings (16-byte aligned) and directions in the layout of merkle_verify_batch; heights on the host."""
+        return self._verify_batch(lib.zigz_dev_merkle_verify_batch, len(heights), vp(d_roots), heights, vp(d_leaves),
+                                  vp(d_siblings), vp(d_dirs))
+
+    def commit_verify_batch(self, commitments, proofs):
+        """CommitmentScheme.batchVerify (polynomial_commit.zig:160-175) on the device, over the input of host.batch_verify:
+        (root, num_vars) pairs and dicts with point, value, index, leaf, siblings and directions.  Returns (all_ok, verdicts).
+        verify's rule per opening (:123-125): a point of another length than num_vars rejects that opening alone; the index and
+        value are not checked.  A path whose directions and siblings differ in number, or higher than any tree (64), is
+        rejected too.  len(commitments) != len(proofs): (False, None), like batchVerify (:164-166)."""
+        k = len(commitments)
+        if k != len(proofs):
+            return False, None
+        verd = np.zeros(k, dtype=np.uint8)
+        sel = [i for i, ((_, v), p) in enumerate(zip(commitments, proofs))
+               if len(p["point"]) == v and len(p["siblings"]) == 32 * len(p["directions"]) and len(p["directions"]) <= 64]
+        if sel:
+            got = self.merkle_verify_batch(b"".join(bytes(commitments[i][0]) for i in sel), [len(proofs[i]["directions"]) for i in sel],
+                                           [int(proofs[i]["leaf"]) for i in sel], b"".join(bytes(proofs[i]["siblings"]) for i in sel),
+                                           b"".join(bytes(proofs[i]["directions"]) for i in sel))
+            verd[sel] = got
+        return bool(verd.all()), verd
+
     def lasso_prove_batch(self, instances):
         """zigz_lasso_prove_batch: instances are dicts with table, queries and optional n_in (2), n_out (1), mapping (None).
         Returns the list of lasso_prove() dicts."""

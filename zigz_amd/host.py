@@ -58,6 +58,7 @@ SIGNATURES = {
                                           u8p, szp]),
     "zigzh_commit_open_verify": (C.c_int, [vp, u64p, C.c_size_t, u64p, C.c_size_t, u8p, u64p, u64p, C.POINTER(C.c_int)]),
     "zigzh_batch_verify": (C.c_int, [u8p, szp, C.c_size_t, u64p, u64p, u64p, u64p, u8p, u8p, C.POINTER(C.c_int)]),
+    "zigzh_batch_verify_dev": (C.c_int, [C.c_void_p, u8p, szp, C.c_size_t, u64p, u64p, u64p, u64p, u8p, u8p, u8p, C.POINTER(C.c_int)]),
 }
 for _n, (_r, _a) in SIGNATURES.items():
     _f = getattr(lib, _n)
@@ -114,6 +115,30 @@ def batch_verify(commitments, proofs):
     _check(lib.zigzh_batch_verify(roots.ctypes.data_as(u8p), nv, k, pp, vlp, ip, lp, sib.ctypes.data_as(u8p),
                                   dirs.ctypes.data_as(u8p), C.byref(ok)))
     return bool(ok.value)
+
+
+def batch_verify_dev(ctx, commitments, proofs):
+    """CommitmentScheme::batchVerify(ctx, ...) of the C++ host (zigzh_batch_verify_dev): batch_verify's input and layout, the
+    openings checked on ctx's device.  Returns (all_ok, verdicts); a proof whose arrays do not match num_vars: (False, None)."""
+    k = len(commitments)
+    if k != len(proofs):
+        return False, None
+    for (_, v), p in zip(commitments, proofs):  # the C arrays are laid out by num_vars
+        if len(p["point"]) != v or len(p["siblings"]) != 32 * v or len(p["directions"]) != v:
+            return False, None
+    roots = np.frombuffer(b"".join(bytes(r) for r, _ in commitments) or b"\0", dtype=np.uint8).copy()
+    nv = (C.c_size_t * max(k, 1))(*[int(v) for _, v in commitments])
+    pts, pp = _u64(np.concatenate([np.asarray(p["point"], dtype=np.uint64).reshape(-1) for p in proofs] + [np.zeros(0, np.uint64)]))
+    vals, vlp = _u64([p["value"] for p in proofs])
+    idx, ip = _u64([p["index"] for p in proofs])
+    leaf, lp = _u64([p["leaf"] for p in proofs])
+    sib = np.frombuffer(b"".join(p["siblings"] for p in proofs) + b"\0", dtype=np.uint8).copy()
+    dirs = np.frombuffer(b"".join(p["directions"] for p in proofs) + b"\0", dtype=np.uint8).copy()
+    verd = np.zeros(max(k, 1), dtype=np.uint8)
+    ok = C.c_int(0)
+    _check(lib.zigzh_batch_verify_dev(ctx.h, roots.ctypes.data_as(u8p), nv, k, pp, vlp, ip, lp, sib.ctypes.data_as(u8p),
+                                      dirs.ctypes.data_as(u8p), verd.ctypes.data_as(u8p), C.byref(ok)))
+    return bool(ok.value), verd[:k].copy()
 
 
 TIMING_NAMES = ["commit_begin", "sumcheck_transcript", "lasso_transcript", "wait_roots", "roots_challenges", "open_all",
