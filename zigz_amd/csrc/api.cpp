@@ -21,12 +21,11 @@ zigz_status ws_get(zigz_ctx *ctx, int slot, size_t bytes, void **out) {
             ctx->ws[slot] = nullptr;
             ctx->ws_bytes[slot] = 0;
         }
-        size_t want = bytes + bytes / 8;  // a little slack so slowly growing sizes do not realloc each call
-        want = (want + 255) & ~(size_t)255;
+        size_t want = align256(bytes + bytes / 8);  // a little slack so slowly growing sizes do not realloc each call
         hipError_t e = hipMalloc(&ctx->ws[slot], want);
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            want = (bytes + 255) & ~(size_t)255;
+            want = align256(bytes);
             e = hipMalloc(&ctx->ws[slot], want);
             if (e != hipSuccess) {
                 (void)hipGetLastError();  // (not left behind for the next launch check on this thread to find)
@@ -117,6 +116,42 @@ DoneFlag done_flag(zigz_ctx *ctx, int which) {  // which: 0 = the roots of a com
     d.flag = (unsigned long long *)(ctx->h_roots + ROOTS_MAX_COLS * 32 + JOB_SUMMARY_WORDS * 8) + which;
     d.seq = ++ctx->done_seq;
     return d;
+}
+// waits for what a launch publishes under `done`: polls its completion word (sleeping, or spinning), then asks the runtime, whose
+// wait also reports a fault.  Timing mode goes straight to the runtime's wait, which returns once the publishing launch has
+// finished, so the published words are the same either way.
+zigz_status wait_published(zigz_ctx *ctx, const DoneFlag &done) {
+    const bool seen = !ctx->timing && (g_sleep_wait.load() ? sleep_wait(done.flag, done.seq) : spin_wait(done.flag, done.seq));
+    if (!seen) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return ZIGZ_OK;
+}
+
+// pinned host memory of `bytes` for one call of a batched entry: the context's staging buffer when it fits, else the batch
+// region, grown (after the stream has drained: launches may still read the old one) and never shrunk
+zigz_status pinned(zigz_ctx *ctx, size_t bytes, uint8_t **out) {
+    if (bytes <= PIN_WORDS * 8) {
+        *out = (uint8_t *)ctx->h_pin;
+        return ZIGZ_OK;
+    }
+    if (ctx->h_batch_bytes < bytes) {
+        if (ctx->h_batch) {
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            (void)hipHostFree(ctx->h_batch);
+            ctx->h_batch = nullptr;
+            ctx->h_batch_bytes = 0;
+        }
+        const size_t want = align256(bytes + bytes / 8);
+        HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_batch, want, hipHostMallocDefault));
+        ctx->h_batch_bytes = want;
+    }
+    *out = (uint8_t *)ctx->h_batch;
+    return ZIGZ_OK;
+}
+
+// a batched entry's failure at entry i: i into *bad_index (when asked for), the status returned
+zigz_status fail_at(size_t *bad_index, size_t i, zigz_status st) {
+    if (bad_index) *bad_index = i;
+    return st;
 }
 
 extern "C" zigz_status zigz_device_set_blocking_sync(int device, int on) {
@@ -461,7 +496,7 @@ static zigz_status witness_from_steps32(zigz_ctx *ctx, const zigz_trace_step32 *
     const size_t npad = (size_t)1 << nv;
     if (num_steps > npad || (nv > 0 && num_steps <= npad / 2) || col_stride < npad) return ZIGZ_ERR_INVALID_ARGUMENT;
     // staging: [48-byte records the expansion reads | the 32-byte records as uploaded | the side list]
-    const size_t wide_b = (num_steps * sizeof(zigz_trace_step) + 255) & ~(size_t)255, raw_b = (num_steps * 32 + 255) & ~(size_t)255;
+    const size_t wide_b = align256(num_steps * sizeof(zigz_trace_step)), raw_b = align256(num_steps * 32);
     void *d_st, *d_ws;
     CHK(ws_get(ctx, WS_IN64, wide_b + raw_b + num_mem * 16 + 256, &d_st));
     CHK(ws_get(ctx, WS_WITNESS, witness_steps_ws_words(npad) * 4, &d_ws));
@@ -509,8 +544,7 @@ static zigz_status witness_from_steps16(zigz_ctx *ctx, const zigz_trace_step16 *
     const size_t npad = (size_t)1 << nv;
     if (num_steps > npad || (nv > 0 && num_steps <= npad / 2) || col_stride < npad) return ZIGZ_ERR_INVALID_ARGUMENT;
     // staging: [48-byte records the expansion reads | the 16-byte records as uploaded | the side list | the code table]
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t wide_b = al(num_steps * sizeof(zigz_trace_step)), raw_b = al(num_steps * 16), mem_b = al(num_mem * 16);
+    const size_t wide_b = align256(num_steps * sizeof(zigz_trace_step)), raw_b = align256(num_steps * 16), mem_b = align256(num_mem * 16);
     void *d_st, *d_ws;
     CHK(ws_get(ctx, WS_IN64, wide_b + raw_b + mem_b + num_code * sizeof(zigz_code_entry) + 256, &d_st));
     CHK(ws_get(ctx, WS_WITNESS, witness_steps_ws_words(npad) * 4, &d_ws));

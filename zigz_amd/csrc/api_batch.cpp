@@ -1,12 +1,13 @@
 // C ABI of libzigz_hip.so, part 5: the batched provers -- k independent sumchecks (and Lasso proofs) in shared launches.
 //
-// Schedule (DESIGN.md "Batched provers"): every table keeps the single-table radix schedule of api_mle.cpp (radix_run) -- a
-// table of n > HOST_TAIL_MAX elements runs a block-sums pass with k = min(log n - 8, 10), then folds until m <= 1024; a
-// smaller one goes straight to the tail -- but each GPU pass serves EVERY table still in play in one launch (sumcheck_batch.hip),
-// and between passes the host runs each table's k rounds on its own block sums with its own transcript.  Tables that finish
-// early drop out of later passes; all remaining tables are read back in one hand-off.  Exact arithmetic throughout, so every
-// table's rounds, point and final_eval are those of a call of its own.
+// Schedule (DESIGN.md "Batched provers"): every table keeps the single-table radix schedule (radix_host.hpp, shared with
+// radix_run in api_mle.cpp) -- a table of n > HOST_TAIL_MAX elements runs a block-sums pass with k = min(log n - 8, 10), then
+// folds until m <= 1024; a smaller one goes straight to the tail -- but each GPU pass serves EVERY table still in play in one
+// launch (sumcheck_batch.hip), and between passes the host runs each table's k rounds on its own block sums with its own
+// transcript (RadixProver).  Tables that finish early drop out of later passes; all remaining tables are read back in one
+// hand-off.  Exact arithmetic throughout, so every table's rounds, point and final_eval are those of a call of its own.
 #include "api_internal.hpp"
+#include "radix_host.hpp"
 
 #include <algorithm>
 #include <array>
@@ -38,15 +39,6 @@ struct LassoOut {
     uint64_t *rounds, *point;
 };
 
-inline uint64_t b_add(uint64_t a, uint64_t b) { uint64_t s = a + b; return s >= P ? s - P : s; }
-inline uint64_t b_sub(uint64_t a, uint64_t b) { return a >= b ? a - b : a + P - b; }
-inline uint64_t b_mul(uint64_t a, uint64_t b) { return (uint64_t)(((unsigned __int128)a * b) % P); }
-
-inline unsigned stage_k(size_t len) {  // radix_run: k = min(log2 len - 8, RADIX_MAX_K) for len > HOST_TAIL_MAX
-    const unsigned l = log2_floor(len);
-    return l - 8 < RADIX_MAX_K ? l - 8 : RADIX_MAX_K;
-}
-
 // Host threads for the per-table rounds of a pass: up to 8, each with at least 4 tables (one table's k <= 10 rounds are a SHA3
 // challenge per round plus O(2^k) scalar field work, of the order of a thread start).  Not tuned yet: the 16 x 2^20 batch is
 // bound by these rounds, so the count is the first thing to sweep.
@@ -76,64 +68,7 @@ void parallel_for(size_t count, F &&fn) {
     for (auto &t : th) t.join();
 }
 
-struct TabState {
-    size_t len = 0;        // current length of the table
-    unsigned k = 0;        // the stage being run (block sums of 2^k blocks)
-    size_t round = 0, nv = 0;
-    uint64_t *rounds = nullptr, *point = nullptr;
-    const uint64_t *fixed = nullptr;
-    Transcript tr;  // fresh per table, sumcheck_protocol.zig:161
-    std::vector<uint64_t> B, W;
-    zigz_status st = ZIGZ_OK;
-
-    uint64_t challenge(uint64_t c0, uint64_t c1) {  // generateChallenge, sumcheck_protocol.zig:176-184
-        rounds[2 * round] = c0;
-        rounds[2 * round + 1] = c1;
-        uint64_t ch;
-        if (fixed) {
-            ch = fixed[round];
-            if (ch >= P) st = ZIGZ_ERR_NOT_CANONICAL;
-        } else {
-            tr.append_field(c0);
-            tr.append_field(c1);
-            ch = tr.challenge();
-        }
-        point[round++] = ch;
-        return ch;
-    }
-    // k rounds on the block-sums table B (MSB-first, like partialEval); leaves the eq weights of the k challenges in W
-    void stage_rounds() {
-        for (auto &b : B) b %= P;
-        W.assign(1, 1);
-        for (unsigned j = 0; j < k && st == ZIGZ_OK; j++) {
-            const size_t half = B.size() / 2;
-            uint64_t s0 = 0, s1 = 0;
-            for (size_t x = 0; x < half; x++) { s0 = b_add(s0, B[x]); s1 = b_add(s1, B[x + half]); }
-            const uint64_t ch = challenge(s0, b_sub(s1, s0));
-            for (size_t x = 0; x < half; x++) B[x] = b_add(B[x], b_mul(ch, b_sub(B[x + half], B[x])));
-            B.resize(half);
-            std::vector<uint64_t> W2(W.size() * 2);
-            const uint64_t one_minus = b_sub(1, ch);
-            for (size_t x = 0; x < W.size(); x++) { W2[2 * x] = b_mul(W[x], one_minus); W2[2 * x + 1] = b_mul(W[x], ch); }
-            W.swap(W2);
-        }
-    }
-    // the last rounds on the remaining <= 1024-entry table
-    uint64_t tail_rounds(std::vector<uint64_t> &tail) {
-        while (tail.size() > 1 && st == ZIGZ_OK) {
-            const size_t half = tail.size() / 2;
-            uint64_t s0 = 0, s1 = 0;
-            for (size_t x = 0; x < half; x++) { s0 = b_add(s0, tail[x]); s1 = b_add(s1, tail[x + half]); }
-            const uint64_t ch = challenge(s0, b_sub(s1, s0));
-            for (size_t x = 0; x < half; x++) tail[x] = b_add(tail[x], b_mul(ch, b_sub(tail[x + half], tail[x])));
-            tail.resize(half);
-        }
-        if (st == ZIGZ_OK && round != nv) st = ZIGZ_ERR_PROTOCOL_ERROR;  // sumcheck_prover.zig:80-82
-        return tail.empty() ? 0 : tail[0];
-    }
-};
-
-zigz_status first_error(const std::vector<TabState> &t) {
+zigz_status first_error(const std::vector<RadixProver> &t) {
     for (const auto &s : t)
         if (s.st != ZIGZ_OK) return s.st;
     return ZIGZ_OK;
@@ -143,7 +78,7 @@ zigz_status first_error(const std::vector<TabState> &t) {
 zigz_status radix_run_batch(zigz_ctx *ctx, const BatchOps &ops, size_t k, const size_t *ns, const uint64_t *fixed,
                             uint64_t *rounds, uint64_t *points, uint64_t *final_evals) {
     ZIGZ_NOTHROW_BEGIN
-    std::vector<TabState> t(k);
+    std::vector<RadixProver> t(k);
     size_t off = 0;
     for (size_t i = 0; i < k; i++) {
         t[i].len = ns[i];
@@ -157,9 +92,8 @@ zigz_status radix_run_batch(zigz_ctx *ctx, const BatchOps &ops, size_t k, const 
     std::vector<unsigned> ks, knext;
     std::vector<uint64_t> sums, weights;
     for (size_t i = 0; i < k; i++)
-        if (ns[i] > HOST_TAIL_MAX) {
+        if ((t[i].k = radix_stage_k(ns[i]))) {
             live.push_back(i);
-            t[i].k = stage_k(ns[i]);
             ks.push_back(t[i].k);
         }
     if (!live.empty()) {
@@ -181,7 +115,7 @@ zigz_status radix_run_batch(zigz_ctx *ctx, const BatchOps &ops, size_t k, const 
         knext.clear();
         for (size_t i : live) {
             const size_t m = t[i].len >> t[i].k;
-            const unsigned kn = m <= HOST_TAIL_MAX ? 0 : stage_k(m);
+            const unsigned kn = radix_stage_k(m);
             ks.push_back(t[i].k);
             knext.push_back(kn);
             wn += t[i].W.size();
@@ -198,7 +132,7 @@ zigz_status radix_run_batch(zigz_ctx *ctx, const BatchOps &ops, size_t k, const 
         idx2.clear();
         o = 0;
         for (size_t j = 0; j < live.size(); j++) {
-            TabState &s = t[live[j]];
+            RadixProver &s = t[live[j]];
             s.len >>= s.k;
             if (!knext[j]) continue;
             s.k = knext[j];
@@ -247,15 +181,6 @@ struct GpuBatch {
     size_t tail_desc_off, weights_off;  // inside the staging area
 };
 
-constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// waits for what a launch publishes under `done`
-zigz_status wait_published(zigz_ctx *ctx, const DoneFlag &done) {
-    const bool seen = !ctx->timing && (g_sleep_wait.load() ? sleep_wait(done.flag, done.seq) : spin_wait(done.flag, done.seq));
-    if (!seen) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return ZIGZ_OK;
-}
-
 BatchPublish make_pub(const DoneFlag &done, void *h_dst, unsigned long long *d_sums, size_t n) {
     BatchPublish p;
     p.h_dst = h_dst;
@@ -277,8 +202,7 @@ zigz_status gpu_batch_init(zigz_ctx *ctx, GpuBatch &g, size_t k, const uint32_t 
     g.parity.assign(k, 0);
     size_t sums_w = 0, part_w = 0, out_w = 0, w_words = 0, tail_w = 0;
     for (size_t i = 0; i < k; i++) {
-        if (ns[i] > HOST_TAIL_MAX) {
-            const unsigned kk = stage_k(ns[i]);
+        if (const unsigned kk = radix_stage_k(ns[i])) {
             const size_t nb = (size_t)1 << kk, m0 = ns[i] >> kk, groups = radix_fold_groups(nb);
             g.part_off[i] = part_w;
             g.out_off[i] = out_w;
@@ -297,24 +221,8 @@ zigz_status gpu_batch_init(zigz_ctx *ctx, GpuBatch &g, size_t k, const uint32_t 
     g.stage_bytes = g.tail_desc_off + desc;
     const size_t out_bytes = align256(std::max(sums_w * 8, tail_w * 4));
     // pinned: the context's buffer when the batch fits it
-    const size_t pin_need = out_bytes + g.stage_bytes;
     uint8_t *pin;
-    if (pin_need <= PIN_WORDS * 8) {
-        pin = (uint8_t *)ctx->h_pin;
-    } else {
-        if (ctx->h_batch_bytes < pin_need) {
-            if (ctx->h_batch) {
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                (void)hipHostFree(ctx->h_batch);
-                ctx->h_batch = nullptr;
-                ctx->h_batch_bytes = 0;
-            }
-            const size_t want = align256(pin_need + pin_need / 8);
-            HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_batch, want, hipHostMallocDefault));
-            ctx->h_batch_bytes = want;
-        }
-        pin = (uint8_t *)ctx->h_batch;
-    }
+    CHK(pinned(ctx, out_bytes + g.stage_bytes, &pin));
     g.h_out = pin;
     g.h_stage = pin + out_bytes;
     // device
@@ -485,11 +393,6 @@ zigz_status table_check(size_t n, const void *table, bool dev, const uint64_t *f
     return ZIGZ_OK;
 }
 
-zigz_status fail_at(size_t *bad_index, size_t i, zigz_status st) {
-    if (bad_index) *bad_index = i;
-    return st;
-}
-
 bool canonical(const uint64_t *v, size_t n) {
     for (size_t j = 0; j < n; j++)
         if (v[j] >= P) return false;
@@ -576,15 +479,7 @@ namespace {
 // what zigz_lasso_prove[_with_mapping] returns for instance `I` before its upload (pre) and after it (post)
 zigz_status lasso_pre(const LassoInst &I) {
     const size_t w = I.n_in + I.n_out;
-    if (I.mapping) {  // proveWithMapping's host equality scan, :185-201 (same order, same codes)
-        if (I.n_queries != I.n_mapping) return ZIGZ_ERR_MAPPING_LENGTH_MISMATCH;
-        if (I.n_queries && (!I.table || !I.queries)) return ZIGZ_ERR_INVALID_ARGUMENT;
-        for (size_t j = 0; j < I.n_queries; j++) {
-            if (I.mapping[j] >= I.table_rows) return ZIGZ_ERR_INVALID_MAPPING;
-            if (memcmp(I.queries + j * w, I.table + I.mapping[j] * w, w * sizeof(uint64_t)) != 0)
-                return ZIGZ_ERR_QUERY_TABLE_MISMATCH;
-        }
-    }
+    if (I.mapping) CHK(lasso_mapping_check(I.table, I.table_rows, I.queries, I.n_queries, w, I.mapping, I.n_mapping));
     if (I.n_queries == 0) return ZIGZ_ERR_NO_QUERIES;  // :108-110
     if (!I.table || !I.queries || w == 0) return ZIGZ_ERR_INVALID_ARGUMENT;
     CHK(mle_check(I.table_rows));  // :124

@@ -585,7 +585,6 @@ static zigz_status job_begin(zigz_ctx *ctx, const uint32_t *d_cols, size_t ncols
 //         pointer by proof * arena size (kernels.hpp: TreeRef::zstride).  The lists get their WORST-CASE room (every node
 //         hashed: affordable at these sizes, ~0.25 GiB per proof at 2^16), so a batched build is never repeated; every column
 //         must be hinted run-aware or member of the content-addressed group (the witness's 43 are: host/prover.cpp).
-static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 static zigz_status job_build_batch_arena(zigz_commit_job *job, const uint32_t *const *srcs, size_t src_stride) {
     zigz_ctx *ctx = job->ctx;
     const size_t nc = job->ncols1, N = job->N, npad = N;
@@ -608,7 +607,7 @@ static zigz_status job_build_batch_arena(zigz_commit_job *job, const uint32_t *c
     t.top = run_top_level(npad);
     // ---- the arena's layout (byte offsets, the same for every proof)
     size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += al256(bytes); return o; };
+    auto take = [&](size_t bytes) { const size_t o = at; at += align256(bytes); return o; };
     const size_t o_cols = take(nc * stride * 4);
     const size_t o_rctr = take(RUN_CTR_WORDS * 8), o_gctr = take(RUN_CTR_WORDS * 8);
     size_t o_rlist = 0, o_rstage = 0, o_bitmap = 0, o_prev = 0, o_woff = 0, o_ubase = 0, o_rstore = 0;
@@ -646,7 +645,7 @@ static zigz_status job_build_batch_arena(zigz_commit_job *job, const uint32_t *c
         }
     }
     const size_t o_upper = take(nc * 512 * 32);
-    const size_t S = al256(at);
+    const size_t S = align256(at);
     if ((size_t)nz * S > ((size_t)48 << 30)) return ZIGZ_ERR_OUT_OF_MEMORY;
     void *w;
     const void *w_before = ctx->ws[WS_BATCH];

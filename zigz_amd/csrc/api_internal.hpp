@@ -149,6 +149,7 @@ constexpr unsigned BATCH_ARENA_MAX_NV = 20;  // largest table of the arena form 
 inline bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
 inline unsigned log2_floor(size_t n) { unsigned l = 0; while (n > 1) { n >>= 1; l++; } return l; }
 inline size_t ceil_pow2(size_t n) { size_t v = 1; while (v < n) v <<= 1; return v; }
+constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 
 // ---- helpers one translation unit needs from another (hidden: not part of the ABI)
@@ -158,6 +159,9 @@ zigz_status ws_get(zigz_ctx *ctx, int slot, size_t bytes, void **out);
 bool sleep_wait(const unsigned long long *flag, unsigned long long seq);
 bool spin_wait(const unsigned long long *flag, unsigned long long seq);
 DoneFlag done_flag(zigz_ctx *ctx, int which);
+zigz_status wait_published(zigz_ctx *ctx, const DoneFlag &done);
+zigz_status pinned(zigz_ctx *ctx, size_t bytes, uint8_t **out);
+zigz_status fail_at(size_t *bad_index, size_t i, zigz_status st);
 zigz_status log_launch(zigz_ctx *ctx, int cls, uint64_t perms, hipEvent_t start, hipEvent_t stop, hipEvent_t first, double *dur_us);
 zigz_status upload_u64(zigz_ctx *ctx, const uint64_t *h_in, size_t n, uint32_t *d_out, bool reduce);
 zigz_status download_u64(zigz_ctx *ctx, const uint32_t *d_in, size_t n, uint64_t *h_out);
@@ -179,6 +183,8 @@ zigz_status dev_eval_folds(zigz_ctx *ctx, const uint32_t *d_cols, size_t col_str
 zigz_status sumcheck_core(zigz_ctx *ctx, const uint32_t *d_in, size_t n, uint32_t *d_scratch,
                                  const uint64_t *fixed, uint64_t *rounds, uint64_t *point, uint64_t *final_eval);
 zigz_status stage_in(zigz_ctx *ctx, const uint64_t *in, size_t n, uint32_t **d_out);
+zigz_status lasso_mapping_check(const uint64_t *table, size_t table_rows, const uint64_t *queries, size_t n_queries, size_t w,
+                                const uint64_t *mapping, size_t n_mapping);
 zigz_status build_trees(zigz_ctx *ctx, const uint32_t *d_vals, size_t val_stride, size_t n_values, size_t npad,
                                uint8_t *d_slab, size_t ncols, bool record = false, TreeRef *ref = nullptr);
 zigz_status keccak_times_collect(zigz_ctx *ctx);

@@ -32,45 +32,11 @@ struct zigz_merkle_batch {
 
 namespace {
 
-constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 constexpr size_t MAX_VALUES = (size_t)1 << 40;  // merkle_tree.zig:287 (the single call's device-size cap)
 
 unsigned stages_of(unsigned h) { return h <= MB_STAGE_LEVELS ? 1 : (h + MB_STAGE_LEVELS - 1) / MB_STAGE_LEVELS; }
 size_t open_desc_bytes(size_t k, size_t sum_h) {
     return align256(k * sizeof(MPathTab)) + align256(k * sizeof(MEvalTab)) + 2 * sum_h * sizeof(uint32_t);
-}
-
-zigz_status fail_at(size_t *bad_index, size_t i, zigz_status st) {
-    if (bad_index) *bad_index = i;
-    return st;
-}
-
-// pinned host memory for one call: the context's staging buffer when it fits, else the (grown, never shrunk) batch region
-zigz_status pinned(zigz_ctx *ctx, size_t bytes, uint8_t **out) {
-    if (bytes <= PIN_WORDS * 8) {
-        *out = (uint8_t *)ctx->h_pin;
-        return ZIGZ_OK;
-    }
-    if (ctx->h_batch_bytes < bytes) {
-        if (ctx->h_batch) {
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipHostFree(ctx->h_batch);
-            ctx->h_batch = nullptr;
-            ctx->h_batch_bytes = 0;
-        }
-        const size_t want = align256(bytes + bytes / 8);
-        HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_batch, want, hipHostMallocDefault));
-        ctx->h_batch_bytes = want;
-    }
-    *out = (uint8_t *)ctx->h_batch;
-    return ZIGZ_OK;
-}
-
-// waits for what a launch publishes under `done` (a short spin, then the runtime's wait, which also reports a fault)
-zigz_status wait_done(zigz_ctx *ctx, const DoneFlag &done) {
-    const bool seen = g_sleep_wait.load() ? sleep_wait(done.flag, done.seq) : spin_wait(done.flag, done.seq);
-    if (!seen) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return ZIGZ_OK;
 }
 
 // Narrows the host tables into the packed u32 staging (table i at word vals_off[i]) and finds the first table holding a
@@ -234,7 +200,7 @@ zigz_status commit_run(zigz_ctx *ctx, const uint32_t *const *d_values, const uin
         const DoneFlag done = done_flag(ctx, 2);
         launch_mbatch_roots(d_tabs, (unsigned)k, h_roots, ctx->stream, done);  // stage 0 holds every tree, in order
         HIPCHK(ctx, hipGetLastError());
-        CHK(wait_done(ctx, done));
+        CHK(wait_published(ctx, done));
         memcpy(roots, h_roots, k * 32);
         if (heights)
             for (size_t i = 0; i < k; i++) heights[i] = b->height[i];
@@ -303,7 +269,7 @@ zigz_status open_run(zigz_ctx *ctx, const zigz_merkle_batch *b, const uint64_t *
     const DoneFlag done = done_flag(ctx, 2);
     launch_mbatch_paths((const MPathTab *)b->d_desc, (unsigned)k, o, ctx->stream, done);
     HIPCHK(ctx, hipGetLastError());
-    CHK(wait_done(ctx, done));
+    CHK(wait_published(ctx, done));
     if (sum_h) {
         memcpy(siblings, o.sib, sum_h * 32);
         memcpy(dirs, o.dirs, sum_h);

@@ -24,32 +24,6 @@ constexpr size_t TABS_BYTES = mv::align256((mv::MAX_HEIGHT + 1) * sizeof(MVerify
 constexpr unsigned PAUSE_MIN_WAVES = 4096;  // launches of at least this many waves hash with the re-arm pauses
 static_assert(sizeof(MVerifyTab) == 40, "descriptor layout");
 
-zigz_status fail_at(size_t *bad_index, size_t i, zigz_status st) {
-    if (bad_index) *bad_index = i;
-    return st;
-}
-
-// pinned host memory of `bytes`: the context's staging buffer when it fits, else the (grown, never shrunk) batch region
-zigz_status pinned(zigz_ctx *ctx, size_t bytes, uint8_t **out) {
-    if (bytes <= PIN_WORDS * 8) {
-        *out = (uint8_t *)ctx->h_pin;
-        return ZIGZ_OK;
-    }
-    if (ctx->h_batch_bytes < bytes) {
-        if (ctx->h_batch) {
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipHostFree(ctx->h_batch);
-            ctx->h_batch = nullptr;
-            ctx->h_batch_bytes = 0;
-        }
-        const size_t want = mv::align256(bytes + bytes / 8);
-        HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_batch, want, hipHostMallocDefault));
-        ctx->h_batch_bytes = want;
-    }
-    *out = (uint8_t *)ctx->h_batch;
-    return ZIGZ_OK;
-}
-
 bool pause_for(const zigz_ctx *ctx, size_t nwg) {
     if (ctx->verify_pause) return ctx->verify_pause == 1;
     return nwg * (MV_TPB / 64) >= PAUSE_MIN_WAVES;
@@ -146,8 +120,7 @@ zigz_status verify_run(zigz_ctx *ctx, bool dev, size_t k, const uint8_t *roots, 
     const DoneFlag done = done_flag(ctx, 2);
     launch_publish_u64(d_rej, 1, h_rej, true, ctx->stream, done);
     HIPCHK(ctx, hipGetLastError());
-    const bool seen = g_sleep_wait.load() ? sleep_wait(done.flag, done.seq) : spin_wait(done.flag, done.seq);
-    if (!seen) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (a fault is reported by the runtime's wait)
+    CHK(wait_published(ctx, done));
     if (verdicts) memcpy(verdicts, h_verd, k);
     *n_rejected = (size_t)*h_rej;
     return ZIGZ_OK;

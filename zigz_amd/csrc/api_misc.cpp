@@ -82,6 +82,19 @@ extern "C" zigz_status zigz_lasso_prove(zigz_ctx *ctx, const uint64_t *table, si
     ZIGZ_NOTHROW_END(ctx)
 }
 
+// proveWithMapping's checks before it proves (:185-201, in its order): the lengths agree, and every query row equals the table
+// row its mapping entry names (an O(Q*w) host-side equality scan of caller data).  Also zigz_lasso_prove_batch's, per instance.
+zigz_status lasso_mapping_check(const uint64_t *table, size_t table_rows, const uint64_t *queries, size_t n_queries, size_t w,
+                                const uint64_t *mapping, size_t n_mapping) {
+    if (n_queries != n_mapping) return ZIGZ_ERR_MAPPING_LENGTH_MISMATCH;  // :185-187
+    if (n_queries && (!table || !queries || !mapping)) return ZIGZ_ERR_INVALID_ARGUMENT;
+    for (size_t j = 0; j < n_queries; j++) {  // :190-201
+        if (mapping[j] >= table_rows) return ZIGZ_ERR_INVALID_MAPPING;
+        if (memcmp(queries + j * w, table + mapping[j] * w, w * sizeof(uint64_t)) != 0) return ZIGZ_ERR_QUERY_TABLE_MISMATCH;
+    }
+    return ZIGZ_OK;
+}
+
 extern "C" zigz_status zigz_lasso_prove_with_mapping(zigz_ctx *ctx, const uint64_t *table, size_t table_rows,
                                                      const uint64_t *queries, size_t n_queries, size_t n_in,
                                                      size_t n_out, const uint64_t *mapping, size_t n_mapping,
@@ -91,14 +104,7 @@ extern "C" zigz_status zigz_lasso_prove_with_mapping(zigz_ctx *ctx, const uint64
     ZIGZ_NOTHROW_BEGIN
     ZIGZ_ENTER(ctx);
     if (!ctx) return ZIGZ_ERR_INVALID_ARGUMENT;
-    if (n_queries != n_mapping) return ZIGZ_ERR_MAPPING_LENGTH_MISMATCH;  // :185-187
-    const size_t w = n_in + n_out;
-    if (n_queries && (!table || !queries || !mapping)) return ZIGZ_ERR_INVALID_ARGUMENT;
-    for (size_t j = 0; j < n_queries; j++) {  // O(Q*w) host-side equality scan of caller data, :190-201
-        if (mapping[j] >= table_rows) return ZIGZ_ERR_INVALID_MAPPING;
-        if (memcmp(queries + j * w, table + mapping[j] * w, w * sizeof(uint64_t)) != 0)
-            return ZIGZ_ERR_QUERY_TABLE_MISMATCH;
-    }
+    CHK(lasso_mapping_check(table, table_rows, queries, n_queries, n_in + n_out, mapping, n_mapping));
     return zigz_lasso_prove(ctx, table, table_rows, queries, n_queries, n_in, n_out, nv_out, rounds, point, final_eval,
                             query_commitment, table_commitment);
     ZIGZ_NOTHROW_END(ctx)

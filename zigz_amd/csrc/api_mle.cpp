@@ -1,6 +1,7 @@
 // C ABI of libzigz_hip.so, part 2: the MLE operations (bind, round sums, eval) and the sumcheck provers (per-round, radix, sharded by
 // rows over several GPUs).  The only host arithmetic is the sequential SHA3 Fiat-Shamir sponge and O(v) scalar bookkeeping.
 #include "api_internal.hpp"
+#include "radix_host.hpp"
 
 using namespace zk;
 
@@ -284,7 +285,10 @@ zigz_status sumcheck_core(zigz_ctx *ctx, const uint32_t *d_in, size_t n, uint32_
     HIPCHK(ctx, hipGetLastError());
     uint64_t s[2];
     CHK(read_u64(ctx, ctx->d_sums, 2, s));
-    Transcript tr;  // fresh transcript per sumcheck, sumcheck_protocol.zig:161
+    RadixProver sc;  // (its challenge step only)
+    sc.rounds = rounds;
+    sc.point = point;
+    sc.fixed = fixed;
     bind_pool_reset(ctx);
     const uint32_t *cur = d_in;
     size_t len = n;
@@ -292,18 +296,8 @@ zigz_status sumcheck_core(zigz_ctx *ctx, const uint32_t *d_in, size_t n, uint32_
     for (size_t round = 0; round < nv; round++) {
         uint64_t c0 = s[0] % P, s1 = s[1] % P;
         uint64_t c1 = s1 >= c0 ? s1 - c0 : s1 + P - c0;  // roundPolynomial: [q(0), q(1)-q(0)], multilinear.zig:228-229
-        rounds[2 * round] = c0;
-        rounds[2 * round + 1] = c1;
-        uint64_t ch;
-        if (fixed) {
-            ch = fixed[round];
-            if (ch >= P) return ZIGZ_ERR_NOT_CANONICAL;
-        } else {
-            tr.append_field(c0);  // generateChallenge, sumcheck_protocol.zig:176-184
-            tr.append_field(c1);
-            ch = tr.challenge();
-        }
-        point[round] = ch;
+        const uint64_t ch = sc.challenge(c0, c1);
+        CHK(sc.st);
         uint32_t *dst = (round % 2 == 0) ? bufA : bufB;
         const bool last = (len == 2);
         if (ctx->timing) CHK(timed_begin(ctx, 0));
@@ -343,12 +337,8 @@ zigz_status sumcheck_core(zigz_ctx *ctx, const uint32_t *d_in, size_t n, uint32_
 //   pass 2  GPU: T'[i] = sum_b eq(r_0..r_{k-1}; b) * T[b*m + i]  (one more read, writes n/2^k) + next block sums
 // i.e. two passes over the table per k <= 10 rounds and two host round trips instead of k.  The O(n) data work
 // stays on the GPU; the host touches only the <= 1024-entry sums tables (and the final <= 1024-entry table).
-// Exact field arithmetic => identical round polynomials, challenges and final_eval (tests compare both forms).
-namespace {
-inline uint64_t h_add(uint64_t a, uint64_t b) { uint64_t s = a + b; return s >= P ? s - P : s; }
-inline uint64_t h_sub(uint64_t a, uint64_t b) { return a >= b ? a - b : a + P - b; }
-inline uint64_t h_mul(uint64_t a, uint64_t b) { return (uint64_t)(((unsigned __int128)a * b) % P); }
-}  // namespace
+// Exact field arithmetic => identical round polynomials, challenges and final_eval (tests compare both forms).  The host
+// rounds are radix_host.hpp's, shared with the batched prover.
 
 // The radix sumcheck as orchestration over three data passes (RadixOps) and, when the table is sharded by rows over
 // several GPUs, one exchange hook.  Row sharding: global index i lives on rank i mod G at local index
@@ -380,23 +370,12 @@ zigz_status radix_run(zigz_ctx *ctx, const RadixOps &ops, size_t n_local, const 
                       uint64_t *rounds, uint64_t *point, uint64_t *final_eval) {
     ZIGZ_NOTHROW_BEGIN
     const size_t world = comm && comm->world > 1 ? (size_t)comm->world : 1;
-    const unsigned nv = log2_floor(n_local) + log2_floor(world);
-    Transcript tr;  // fresh transcript per sumcheck, sumcheck_protocol.zig:161
-    size_t round = 0;
-    auto next_challenge = [&](uint64_t c0, uint64_t c1, uint64_t *ch) -> zigz_status {
-        rounds[2 * round] = c0;
-        rounds[2 * round + 1] = c1;
-        if (fixed) {
-            if (fixed[round] >= P) return ZIGZ_ERR_NOT_CANONICAL;
-            *ch = fixed[round];
-        } else {
-            tr.append_field(c0);  // generateChallenge, sumcheck_protocol.zig:176-184
-            tr.append_field(c1);
-            *ch = tr.challenge();
-        }
-        point[round++] = *ch;
-        return ZIGZ_OK;
-    };
+    RadixProver s;
+    s.len = n_local;
+    s.nv = log2_floor(n_local) + log2_floor(world);  // (the rank bits are variables too)
+    s.rounds = rounds;
+    s.point = point;
+    s.fixed = fixed;
     std::vector<uint64_t> gather, wire;
     // One exchange: every rank contributes `v` (all ranks the same length) behind ONE status word.  A rank whose local pass
     // failed still takes part -- with its status and a zero payload -- so that all ranks leave the proof at the same
@@ -443,42 +422,26 @@ zigz_status radix_run(zigz_ctx *ctx, const RadixOps &ops, size_t n_local, const 
         }
         return ZIGZ_OK;
     };
-    std::vector<uint64_t> B, W, tail;
-    size_t len = n_local;
-    if (len > HOST_TAIL_MAX) {
-        unsigned k = log2_floor(len) - 8 < RADIX_MAX_K ? log2_floor(len) - 8 : RADIX_MAX_K;
-        B.assign((size_t)1 << k, 0);
-        ZK_LOCAL(ops.block_sums(ops.user, k, B.data()));
-        CHK(sum_over_ranks(B));
+    if ((s.k = radix_stage_k(s.len))) {
+        s.B.assign((size_t)1 << s.k, 0);
+        ZK_LOCAL(ops.block_sums(ops.user, s.k, s.B.data()));
+        CHK(sum_over_ranks(s.B));
         for (;;) {
-            for (auto &b : B) b %= P;
-            W.assign(1, 1);
-            for (unsigned j = 0; j < k; j++) {  // k rounds on the block-sums table (MSB-first, like partialEval)
-                const size_t half = B.size() / 2;
-                uint64_t s0 = 0, s1 = 0;
-                for (size_t x = 0; x < half; x++) { s0 = h_add(s0, B[x]); s1 = h_add(s1, B[x + half]); }
-                uint64_t ch;
-                CHK(next_challenge(s0, h_sub(s1, s0), &ch));
-                for (size_t x = 0; x < half; x++) B[x] = h_add(B[x], h_mul(ch, h_sub(B[x + half], B[x])));
-                B.resize(half);
-                std::vector<uint64_t> W2(W.size() * 2);
-                const uint64_t one_minus = h_sub(1, ch);
-                for (size_t x = 0; x < W.size(); x++) { W2[2 * x] = h_mul(W[x], one_minus); W2[2 * x + 1] = h_mul(W[x], ch); }
-                W.swap(W2);
-            }
-            const size_t m = len >> k;
-            const unsigned lm = log2_floor(m);
-            const unsigned k_next = m <= HOST_TAIL_MAX ? 0 : (lm - 8 < RADIX_MAX_K ? lm - 8 : RADIX_MAX_K);
-            B.assign(k_next ? (size_t)1 << k_next : 0, 0);
-            ZK_LOCAL(ops.fold(ops.user, k, W.data(), k_next, k_next ? B.data() : nullptr));
-            len = m;
+            s.stage_rounds();
+            CHK(s.st);
+            const size_t m = s.len >> s.k;
+            const unsigned k_next = radix_stage_k(m);
+            s.B.assign(k_next ? (size_t)1 << k_next : 0, 0);
+            ZK_LOCAL(ops.fold(ops.user, s.k, s.W.data(), k_next, k_next ? s.B.data() : nullptr));
+            s.len = m;
             if (!k_next) break;
-            CHK(sum_over_ranks(B));
-            k = k_next;
+            CHK(sum_over_ranks(s.B));
+            s.k = k_next;
         }
     }
     // the remaining table: len local entries per rank, global index j*G + g
-    std::vector<uint64_t> mine(len);
+    const size_t len = s.len;
+    std::vector<uint64_t> mine(len), tail;
     ZK_LOCAL(ops.read_tail(ops.user, len, mine.data()));
 #undef ZK_LOCAL
     if (world == 1) {
@@ -492,17 +455,9 @@ zigz_status radix_run(zigz_ctx *ctx, const RadixOps &ops, size_t n_local, const 
                 tail[j * world + r] = gather[r * len + j];
             }
     }
-    while (tail.size() > 1) {  // last rounds on the <= 1024 * G entry table, identical on every rank
-        const size_t half = tail.size() / 2;
-        uint64_t s0 = 0, s1 = 0;
-        for (size_t x = 0; x < half; x++) { s0 = h_add(s0, tail[x]); s1 = h_add(s1, tail[x + half]); }
-        uint64_t ch;
-        CHK(next_challenge(s0, h_sub(s1, s0), &ch));
-        for (size_t x = 0; x < half; x++) tail[x] = h_add(tail[x], h_mul(ch, h_sub(tail[x + half], tail[x])));
-        tail.resize(half);
-    }
-    if (round != nv) return ZIGZ_ERR_PROTOCOL_ERROR;  // sumcheck_prover.zig:80-82
-    *final_eval = tail[0];
+    const uint64_t fe = s.tail_rounds(tail);  // the last rounds on the <= 1024 * G entry table, identical on every rank
+    CHK(s.st);
+    *final_eval = fe;
     return ZIGZ_OK;
     ZIGZ_NOTHROW_END(ctx)
 }
@@ -531,19 +486,9 @@ struct GpuRadix {
 // command and a stream wait cost 15-25 us a time, a sumcheck of 2^24 entries is 30 us of data passes and three such hand-overs.
 // rezero: the words are left zero (the sums of a later pass accumulate into them).  Many waiting threads (blocking sync): the
 // sleeping wait, as in the commit path.
-static zigz_status published(zigz_ctx *ctx, const DoneFlag &done, size_t n, bool u32, uint64_t *out);
-static zigz_status publish_out(zigz_ctx *ctx, void *d_src, size_t n, bool u32, bool rezero, uint64_t *out) {
-    if (n > PIN_WORDS / 4) return ZIGZ_ERR_INVALID_ARGUMENT;
-    const DoneFlag done = done_flag(ctx, 2);
-    if (u32) launch_publish_u32((const uint32_t *)d_src, n, (uint32_t *)ctx->h_pin, ctx->stream, done);
-    else launch_publish_u64((unsigned long long *)d_src, n, (unsigned long long *)ctx->h_pin, rezero, ctx->stream, done);
-    HIPCHK(ctx, hipGetLastError());
-    return published(ctx, done, n, u32, out);
-}
 // waits for what a kernel has been asked to publish into ctx->h_pin under `done`, and hands it out
 static zigz_status published(zigz_ctx *ctx, const DoneFlag &done, size_t n, bool u32, uint64_t *out) {
-    const bool seen = !ctx->timing && (g_sleep_wait.load() ? sleep_wait(done.flag, done.seq) : spin_wait(done.flag, done.seq));
-    if (!seen) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    CHK(wait_published(ctx, done));
     if (u32) {
         const uint32_t *h = (const uint32_t *)ctx->h_pin;
         for (size_t i = 0; i < n; i++) out[i] = h[i];
@@ -551,6 +496,14 @@ static zigz_status published(zigz_ctx *ctx, const DoneFlag &done, size_t n, bool
         memcpy(out, ctx->h_pin, n * 8);
     }
     return ZIGZ_OK;
+}
+static zigz_status publish_out(zigz_ctx *ctx, void *d_src, size_t n, bool u32, bool rezero, uint64_t *out) {
+    if (n > PIN_WORDS / 4) return ZIGZ_ERR_INVALID_ARGUMENT;
+    const DoneFlag done = done_flag(ctx, 2);
+    if (u32) launch_publish_u32((const uint32_t *)d_src, n, (uint32_t *)ctx->h_pin, ctx->stream, done);
+    else launch_publish_u64((unsigned long long *)d_src, n, (unsigned long long *)ctx->h_pin, rezero, ctx->stream, done);
+    HIPCHK(ctx, hipGetLastError());
+    return published(ctx, done, n, u32, out);
 }
 zigz_status sums_out(GpuRadix *g, unsigned long long *d_sums, size_t n, zigz_status st, uint64_t *out) {
     zigz_ctx *ctx = g->ctx;
@@ -668,9 +621,7 @@ static zigz_status sumcheck_radix_sharded(zigz_ctx *ctx, const uint32_t *d_in, s
                                           const uint64_t *fixed, uint64_t *rounds, uint64_t *point, uint64_t *final_eval,
                                           zigz_rccl_comm *rccl = nullptr) {
     GpuRadix g{ctx, d_in, n, 0, nullptr, nullptr, nullptr, 0, rccl};
-    if (n > HOST_TAIL_MAX) {
-        const unsigned lv = log2_floor(n);
-        const unsigned k = lv - 8 < RADIX_MAX_K ? lv - 8 : RADIX_MAX_K;
+    if (const unsigned k = radix_stage_k(n)) {
         g.m0 = n >> k;
         const size_t g0 = radix_fold_groups((size_t)1 << k);
         void *ws;
