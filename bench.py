@@ -2,7 +2,12 @@
 """bench.py -- trace steps/sec proved on the synthetic RV64I ADD/XOR loop at a 2^20 trace (BASELINE config 3).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--nv 20] [--mode traces|shard]
-                    [--no-cpu-baseline] [--kernels] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-extras]] [--kernels] [--dump-outputs DIR]
+
+A plain run does only what the headline needs: it sets up the lanes, warms up, times K steps, writes --dump-outputs and prints
+the line (metric / value / unit / ms_per_step / ... and `config`).  Everything else it can measure or check -- the CPU
+baseline, the roofline leg, the legs on other traces, sizes and Merkle builds, the self-check, the per-kernel leg, the
+one-proof-over-all-GPUs leg and the verification of a proof -- runs with `--full` only, after the timed region as before.
 
 A "step" is ONE full pass of the prover hot path over one batch of `--batch` independent 2^20-step traces (default: 8.8 per
 sponge-server thread -- 8 slots each and a tenth more proofs than slots --, 10 servers on a 16-CPU share of the host;
@@ -17,7 +22,7 @@ Why a batch: one proof is bounded by its own sequential SHA3 transcript on ONE h
 concurrently (one host thread + one HIP stream each), and advances their transcripts 8 per host thread in lock step
 (zigz_host_sponge_servers: 8-way AVX-512 Keccak-f, same bytes absorbed) so that the host cores carry them.
 
-The JSON line: metric / value / ... as the contract says; `roofline` = the kernel class that dominates the TIMED REGION
+The JSON line (--full): metric / value / ... as the contract says; `roofline` = the kernel class that dominates the TIMED REGION
 (k_level_hash: permutations x VALU instructions per hash / the sum of its launches' own durations / the int-VALU issue peak;
 flat keys, the named ones first); `config` = the workload plus, measured right after the timed region in the same process,
 single_proof_ms, pcie_inclusive_value (trace upload + witness kernels inside the loop), the same batch on three other traces
@@ -335,6 +340,7 @@ def dump_outputs(path, proofs, prefix="", limit=DUMP_LIMIT_BYTES):
 
 
 def main():
+    t_main = time.perf_counter()
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)  # (1.1 s of timed region: the lanes start in lock step, and the first cycles of a
@@ -386,14 +392,19 @@ def main():
                     "every node")
     ap.add_argument("--dedup", action="store_true", help="same as --merkle all")
     ap.add_argument("--dense-merkle", action="store_true", help="same as --merkle dense")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run every leg beyond the headline (roofline, "
+                    "single proof, GPU-bound, PCIe-inclusive, self-check, Merkle variants, per-kernel, other traces and sizes, one "
+                    "proof over all GPUs; each can be left out below) and the CPU baseline before it, and verify a proof; the line "
+                    "then carries `roofline`, `cpu_baseline` and the legs' figures.  Off: set-up, warm-up, timed steps, line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-sample-cols", type=int, default=12, help="columns of the CPU baseline sample (~1.1 s each)")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--kernels", action="store_true", help="per-kernel leg only (cold-HBM launches, kernel timestamps)")
     ap.add_argument("--lasso", action="store_true", help="Lasso leg only: zigz_lasso_prove end to end (8-bit XOR table, 2^16 rows) "
                     "with 2^16 .. 2^20 queries + the fingerprint kernel, prints its own JSON line")
     ap.add_argument("--kernel-iters", type=int, default=10)
-    ap.add_argument("--no-extras", action="store_true", help="skip the single-proof, PCIe-inclusive and per-kernel legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the legs after the roofline leg (single-proof, "
+                    "PCIe-inclusive, per-kernel, ...)")
     ap.add_argument("--dry-run", action="store_true", help="launcher rehearsal without a GPU: the ranks rendezvous over gloo, "
                     "all-reduce a token and rank 0 prints {dry_run, n_gpus}; nothing is measured")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed region, write the proof every lane produced in the "
@@ -458,10 +469,10 @@ def main():
     def emit(line):
         os.write(result_fd, (line + "\n").encode())
 
-    # ---- CPU baseline first (rank 0, N = 1 only), in a child of its own: the GPU phase that follows is then one
+    # ---- CPU baseline first (--full, rank 0, N = 1 only), in a child of its own: the GPU phase that follows is then one
     # contiguous stretch, and this process never loads the oracle
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and args.cpu_sample_cols > 0 and not args.kernels:
+    if args.full and world == 1 and not args.no_cpu_baseline and args.cpu_sample_cols > 0 and not args.kernels:
         cpu = run_cpu_baseline(args.nv, args.cpu_sample_cols)
 
     dist = None
@@ -828,9 +839,12 @@ def main():
         return time.perf_counter() - t0, acc, phases
 
     main_fn = Lane.upload_and_prove if (args.upload and use_slots) else Lane.prove
+    t_lanes = time.perf_counter()
     run_step(main_fn)  # set-up, not a step: first-use allocation of every lane's workspaces (2.7 GiB of tree each), thread start-up
+    t_first = time.perf_counter()
     for _ in range(args.warmup):
         run_step(main_fn)
+    t_warm = time.perf_counter()
     # Per-launch kernel timestamps (HIP events on every launch's own stream) cost host CPU -- two events per launch, collected
     # per proof, and their completion handlers on the runtime's event thread: ~0.5 ms of the ~8 ms of CPU per proof on a
     # host-bound box.  THE timed region therefore carries none (VERDICT r3 #3d); `roofline` comes from a short leg right after it
@@ -848,6 +862,10 @@ def main():
         import thread_cpu
         snap0 = thread_cpu.snapshot()
     dt, acc, phases = timed(args.steps, main_fn, keep_proofs=bool(args.dump_outputs))  # ---- THE timed region
+    if rank == 0:  # where the wall clock of the run went up to here (the first step is set-up: workspaces, threads)
+        sys.stderr.write("bench.py: set-up %.1f s (%d lanes), first step %.1f s, warm-up %.1f s, timed region %.1f s\n"
+                         % (t_lanes - t_main, B, t_first - t_lanes, t_warm - t_first, dt))
+        sys.stderr.flush()
     if os.environ.get("ZIGZ_BENCH_THREAD_CPU"):
         rows, by = thread_cpu.diff(snap0, thread_cpu.snapshot())
         sys.stderr.write("thread CPU over the timed region (%.2f s wall):\n" % dt)
@@ -891,7 +909,7 @@ def main():
         return tot + (ce - cs)
 
     roof_leg = None
-    if use_slots and not shard:
+    if args.full and use_slots and not shard:
         try:
             ctxs = slots.contexts()
             ctxs[0].set_epoch()
@@ -924,7 +942,7 @@ def main():
 
     # ---- legs outside the timed region (same run, same resident data).  Each runs under a guard: a leg that fails (out of
     # HBM on an unusual box, say) is recorded in detail.leg_errors and left out; the line with `value` goes out regardless.
-    extras = not args.no_extras and not shard
+    extras = args.full and not args.no_extras and not shard
     solo = kern = gpu_one = None
     legs = {}         # name -> {"dt", "steps", "trace_steps", ...}: what is reduced over the ranks below
     leg_errors = {}
@@ -1164,7 +1182,7 @@ def main():
     # --mode shard), reported in the same line.  Exchanges go through the shared-memory hook (host-resident payloads of a
     # few KiB; no device collective), every wait has a timeout, and any failure is recorded instead of losing the line.
     shard_leg = None
-    if world > 1 and not shard and not args.no_extras:
+    if args.full and world > 1 and not shard and not args.no_extras:
         comm = None
         sd = None
         ok = 1.0
@@ -1305,7 +1323,8 @@ def main():
         total_steps = local_steps
 
     if rank == 0:
-        assert host.verify(proof, prog) == "Accept"
+        if args.full:
+            assert host.verify(proof, prog) == "Accept"
         ic = isa_counts()
         # ---- `roofline`: the kernel class that dominates, from the roofline leg (every launch of every proof timed, absolute
         # begin / end).  Per class: launches, sum of durations, UNION of the intervals (time with >= 1 launch of the class on
@@ -1448,6 +1467,11 @@ def main():
                   "class_busy_share_of_wall_roofline_leg": detail_busy,
                   "roofline_leg": {"steps": roof_leg["steps"], "proofs": roof_leg["steps"] * B, "wall_us": wall_us,
                                    "launches_logged": len(roof_leg["recs"])} if roof_leg else None}
+        if not args.full:  # a plain run times no launch of its own: no kernel class has a time, and there is no `roofline`
+            roof = None
+            for k_ in ("kernel_time_shares_roofline_leg", "kernel_us_per_proof_roofline_leg", "class_busy_share_of_wall_roofline_leg",
+                       "roofline_leg"):
+                del detail[k_]
         if roof_leg and roof_leg.get("by_level"):
             # the big levels (0-4 hold 97 % of a proof's hashes and fill the chip alone) against the wall clock of the leg: how much
             # of the time is at least one of them running, how many at once, and how long a launch of each level takes in company
@@ -1462,7 +1486,7 @@ def main():
                 "avg_us_by_level": [round(sum(b - a for a, b in bl[lv]) / len(bl[lv]), 1) for lv in sorted(bl)],
                 "big_levels_0_4_union_share_of_wall": union_us(big) / wall_us if big else None,
                 "big_levels_at_once_share_of_wall": {str(k_): round(v_ / wall_us, 4) for k_, v_ in sorted(hist.items()) if k_ > 0}}
-        for k_ in ("leg_wall_us", "sum_of_durations_us", "eval_hbm_frac"):
+        for k_ in ("leg_wall_us", "sum_of_durations_us", "eval_hbm_frac") if roof is not None else ():
             detail["roofline_" + k_] = roof.pop(k_, None)
         if solo:
             cfg["single_proof_ms"] = solo["dt"] / solo["n"] * 1e3
@@ -1533,7 +1557,7 @@ def main():
         detail["host_keccak"] = zigz_amd._ffi.lib.zigz_host_keccak_impl().decode()
         # (`roofline` stays at 24 flat keys -- what the driver's record keeps per dict --, the figures a reader wants first: the
         # rest moves to detail)
-        for k_ in ("valu_instr_per_hash_kernel_static", "leg_value", "busy_share_of_wall"):
+        for k_ in ("valu_instr_per_hash_kernel_static", "leg_value", "busy_share_of_wall") if roof is not None else ():
             if k_ in roof and len(roof) > 24:
                 detail.setdefault("roofline_more", {})[k_] = roof.pop(k_)
         out = {
@@ -1545,8 +1569,9 @@ def main():
             "higher_is_better": True, "scaling": "strong" if shard else "weak", "vs_baseline": None,
             "dtype": "u32", "data": "synthetic",
             "config": cfg,
-            "roofline": roof,
         }
+        if roof is not None:
+            out["roofline"] = roof
         if cpu is not None:
             out["cpu_baseline"] = cpu
         out["detail"] = detail

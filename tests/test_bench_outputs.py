@@ -93,3 +93,28 @@ def test_bench_dump_outputs_end_to_end(tmp_path):
         ctx.close()
     _check_dump(b, runs[0], proofs[:2], 2)
     _check_dump(b, runs[1], proofs, 3)
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_full_adds_the_legs():
+    """A plain run sets up, warms up, times its steps and prints the line -- no CPU baseline, no roofline leg, no leg after the
+    timed region --; --full runs all of them again and puts their figures into the line."""
+    base = [sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--nv", "16", "--batch", "2"]
+    out = subprocess.run(base, env=_env(), capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    j = json.loads(out.stdout.strip().split("\n")[-1])
+    assert j["unit"] == "trace steps/s" and j["higher_is_better"] is True and j["dtype"] == "u32"
+    assert j["value"] > 0 and j["ms_per_step"] > 0 and j["steps"] == 2 and j["warmup"] == 1
+    assert j["config"]["traces_per_step_per_gpu"] == 2
+    assert "roofline" not in j and "cpu_baseline" not in j and "self_check_ok" not in j["config"]
+    assert "bench.py: leg " not in out.stderr and "cpu_baseline child" not in out.stderr
+    out = subprocess.run(base + ["--full", "--cpu-sample-cols", "1"], env=_env(), capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-3000:]
+    j = json.loads(out.stdout.strip().split("\n")[-1])
+    assert j["value"] > 0 and j["roofline"]["kernel"] == "k_level_hash" and j["roofline"]["launches"] > 0
+    assert j["cpu_baseline"]["value"] > 0 and j["config"]["self_check_ok"] is True
+    assert "leg_errors" not in j["detail"], j["detail"]["leg_errors"]
+    for key in ("single_proof_ms", "pcie_inclusive_value", "gpu_bound_ms_per_proof", "register_worst_case_value",
+                "config4_mixed_value", "straight_line_value", "dense_merkle_value", "value_nv22", "value_nv24"):
+        assert j["config"][key] > 0, key
+    assert j["detail"]["kernel_leg"]

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
-"""Copies what tools/regen_profiles.sh left under gpurun_out/p2_* into profiles/ (r02_ names) and derives the per-kernel HBM
-traffic (profiles/r02_traffic.json, profiles/keccak_traffic.json) from the two PMC passes.  Run from the repo root after the
-gpurun call has merged its output."""
+"""python tools/collect_profiles.py OUTDIR: copies what tools/regen_profiles.sh left in OUTDIR as p2_* into profiles/ (r02_
+names) and derives the per-kernel HBM traffic (profiles/r02_traffic.json, profiles/keccak_traffic.json) from the two PMC passes.  Run from the repo root with the profile
+run's OUTDIR at hand."""
 import collections
 import csv
 import glob
 import json
 import os
 import shutil
+import sys
 
 ROUND = "r02"
 
@@ -27,12 +28,12 @@ def counter(path, name):
 
 
 def main():
-    ff = newest("gpurun_out/p2_pmc_FETCH_SIZE/*/*counter_collection.csv")
-    wf = newest("gpurun_out/p2_pmc_WRITE_SIZE/*/*counter_collection.csv")
-    vf = newest("gpurun_out/p2_pmc_VALU/*/*counter_collection.csv")
+    ff = newest(SRC + "/p2_pmc_FETCH_SIZE/*/*counter_collection.csv")
+    wf = newest(SRC + "/p2_pmc_WRITE_SIZE/*/*counter_collection.csv")
+    vf = newest(SRC + "/p2_pmc_VALU/*/*counter_collection.csv")
     F, W = counter(ff, "FETCH_SIZE"), counter(wf, "WRITE_SIZE")
     V1, V2 = counter(vf, "SQ_INSTS_VALU"), counter(vf, "SQ_ACTIVE_INST_VALU2")
-    kern = json.load(open("gpurun_out/p2_kernels.json"))["kernels"]
+    kern = json.load(open(SRC + "/p2_kernels.json"))["kernels"]
     # The per-kernel leg launches, per kernel name, a known sequence: the measured launches of bench.py --kernels are the
     # LAST `launches` dispatches of each (kernel name, grid) group; set-up launches (fills, the cache-flush sweeps of
     # k_block_sums over the 1 GiB buffer) are told apart by their counter value, so per-kernel figures below take the
@@ -86,7 +87,7 @@ def main():
     shutil.copy(wf, "profiles/%s_pmc_write_size.csv" % ROUND)
     shutil.copy(vf, "profiles/%s_pmc_valu.csv" % ROUND)
     for tag in ("kernels", "b1", "bdef", "lasso", "sumcheck"):
-        shutil.copy(newest("gpurun_out/p2_%s/*/*kernel_stats.csv" % tag), "profiles/%s_%s_kernel_stats.csv" % (ROUND, tag))
+        shutil.copy(newest(SRC + "/p2_%s/*/*kernel_stats.csv" % tag), "profiles/%s_%s_kernel_stats.csv" % (ROUND, tag))
     for src_, dst in (("p2_kernels.json", "kernels.json"), ("p2_kernels_plain.json", "kernels_unprofiled.json"),
                       ("p2_bench.json", "final_bench.json"), ("p2_bench_b1.json", "final_bench_b1.json"),
                       ("p2_bench_s0.json", "final_bench_own_thread_transcripts.json"),
@@ -97,13 +98,13 @@ def main():
                       ("p2_gpu_bound.txt", "gpu_bound_rate.txt"),
                       ("p2_bench_gpus2_rehearsal.json", "bench_gpus2_rehearsal.json"), ("p2_lasso.json", "lasso.json"),
                       ("p2_sumcheck.json", "sumcheck.json"), ("p2_extra.json", "extra.json"), ("p2_configs.jsonl", "configs.jsonl")):
-        if os.path.exists(os.path.join("gpurun_out", src_)):
-            shutil.copy(os.path.join("gpurun_out", src_), "profiles/%s_%s" % (ROUND, dst))
+        if os.path.exists(os.path.join(SRC, src_)):
+            shutil.copy(os.path.join(SRC, src_), "profiles/%s_%s" % (ROUND, dst))
     for tag in ("kernels", "b1", "bdef"):
         print(tag)
         for r in list(csv.DictReader(open("profiles/%s_%s_kernel_stats.csv" % (ROUND, tag))))[:8]:
             print("  %-60s calls=%5s avg_us=%10.2f pct=%s" % (r["Name"][:60], r["Calls"], float(r["AverageNs"]) / 1e3, r.get("Percentage")))
-    one = glob.glob("gpurun_out/p2_one/**/*kernel_trace.csv", recursive=True)
+    one = glob.glob(SRC + "/p2_one/**/*kernel_trace.csv", recursive=True)
     if one:  # the launches of the last of three lone proofs, in order: name, grid, start (us from the first), duration (us)
         rows = sorted(csv.DictReader(open(max(one, key=os.path.getmtime))), key=lambda r: int(r["Start_Timestamp"]))
         rows = [r for r in rows if "keccak" in r["Kernel_Name"] or "k_runs" in r["Kernel_Name"] or "k_cons" in r["Kernel_Name"]]
@@ -129,4 +130,7 @@ def main():
 
 
 if __name__ == "__main__":
+    if len(sys.argv) != 2:
+        sys.exit("usage: python %s OUTDIR  (the directory the profile run wrote)" % sys.argv[0])
+    SRC = sys.argv[1]
     main()

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Copies what tools/regen_profiles_r03.sh left under gpurun_out/p3_* into profiles/ (r03_ names) and derives, per kernel of ONE
-lone 2^20 proof, launches / time / HBM traffic / VALU instructions (profiles/r03_one_proof_kernels.json) and the traffic record
-bench.py reads for `roofline.traffic` (profiles/r03_traffic.json).  Run from the repo root after the gpurun call has merged
-its output."""
+"""python tools/collect_profiles_r03.py OUTDIR: copies what tools/regen_profiles_r03.sh left in OUTDIR as p3_* into profiles/
+(r03_ names) and derives, per kernel of ONE lone 2^20 proof, launches / time / HBM traffic / VALU instructions (profiles/r03_one_proof_kernels.json) and the traffic record
+bench.py reads for `roofline.traffic` (profiles/r03_traffic.json).  Run from the repo root with the profile run's
+OUTDIR at hand."""
 import collections
 import csv
 import glob
@@ -10,6 +10,7 @@ import json
 import os
 import re
 import shutil
+import sys
 
 ROUND = "r03"
 
@@ -46,7 +47,7 @@ def last_build(disp):
 
 
 def main():
-    one = newest("gpurun_out/p3_one/**/*kernel_trace.csv")
+    one = newest(SRC + "/p3_one/**/*kernel_trace.csv")
     rows = sorted(csv.DictReader(open(one)), key=lambda r: int(r["Start_Timestamp"]))
     starts = [i for i, r in enumerate(rows) if "k_runs_stage<true>" in r["Kernel_Name"]]
     build = []
@@ -65,9 +66,9 @@ def main():
         d = dur[short(r["Kernel_Name"])]
         d[0] += 1
         d[1] += (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
-    F = last_build(counters(newest("gpurun_out/p3_one_FETCH/**/*counter_collection.csv"), {"FETCH_SIZE"}))
-    W = last_build(counters(newest("gpurun_out/p3_one_WRITE/**/*counter_collection.csv"), {"WRITE_SIZE"}))
-    V = last_build(counters(newest("gpurun_out/p3_one_VALU/**/*counter_collection.csv"), {"SQ_INSTS_VALU", "SQ_ACTIVE_INST_VALU2"}))
+    F = last_build(counters(newest(SRC + "/p3_one_FETCH/**/*counter_collection.csv"), {"FETCH_SIZE"}))
+    W = last_build(counters(newest(SRC + "/p3_one_WRITE/**/*counter_collection.csv"), {"WRITE_SIZE"}))
+    V = last_build(counters(newest(SRC + "/p3_one_VALU/**/*counter_collection.csv"), {"SQ_INSTS_VALU", "SQ_ACTIVE_INST_VALU2"}))
     per = collections.defaultdict(lambda: {"launches": 0, "us": 0.0, "fetch_bytes": 0.0, "write_bytes": 0.0, "valu_wave_instr": 0.0,
                                            "valu2_wave_instr": 0.0})
     for k, (n, us) in dur.items():
@@ -80,7 +81,7 @@ def main():
         per[k]["valu_wave_instr"] += c.get("SQ_INSTS_VALU", 0.0)
         per[k]["valu2_wave_instr"] += c.get("SQ_ACTIVE_INST_VALU2", 0.0)
     # what the hashing kernels hashed in that proof: the bench trace at 2^20 (stats of the same build through the API)
-    stats_path = "gpurun_out/p3_one_stats.json"
+    stats_path = SRC + "/p3_one_stats.json"
     st = json.load(open(stats_path)) if os.path.exists(stats_path) else {}
     hashes = {"k_level_hash": st.get("list_hash_perms")}
     N = 1 << 20
@@ -130,19 +131,19 @@ def main():
             f, r["launches"], r["us"], r["hbm_bytes"] / 1e6,
             ("  (%.2f x algorithmic)" % r["traffic_ratio"]) if "traffic_ratio" in r else "",
             ("  valu2 %.2f" % r["valu2_share"]) if "valu2_share" in r else ""))
-    shutil.copy(newest("gpurun_out/p3_one_FETCH/**/*counter_collection.csv"), "profiles/%s_pmc_fetch_size.csv" % ROUND)
-    shutil.copy(newest("gpurun_out/p3_one_WRITE/**/*counter_collection.csv"), "profiles/%s_pmc_write_size.csv" % ROUND)
-    shutil.copy(newest("gpurun_out/p3_one_VALU/**/*counter_collection.csv"), "profiles/%s_pmc_valu.csv" % ROUND)
+    shutil.copy(newest(SRC + "/p3_one_FETCH/**/*counter_collection.csv"), "profiles/%s_pmc_fetch_size.csv" % ROUND)
+    shutil.copy(newest(SRC + "/p3_one_WRITE/**/*counter_collection.csv"), "profiles/%s_pmc_write_size.csv" % ROUND)
+    shutil.copy(newest(SRC + "/p3_one_VALU/**/*counter_collection.csv"), "profiles/%s_pmc_valu.csv" % ROUND)
     for tag in ("kernels", "b1", "bdef", "lasso", "sumcheck"):
-        shutil.copy(newest("gpurun_out/p3_%s/**/*kernel_stats.csv" % tag), "profiles/%s_%s_kernel_stats.csv" % (ROUND, tag))
+        shutil.copy(newest(SRC + "/p3_%s/**/*kernel_stats.csv" % tag), "profiles/%s_%s_kernel_stats.csv" % (ROUND, tag))
     for src_, dst in (("p3_kernels.json", "kernels.json"), ("p3_kernels_plain.json", "kernels_unprofiled.json"),
                       ("p3_bench.json", "final_bench.json"), ("p3_bench_b1.json", "final_bench_b1.json"),
                       ("p3_bench_8x8.json", "final_bench_8x8.json"), ("p3_bench_11x8.json", "final_bench_11x8.json"),
                       ("p3_bench_s0.json", "final_bench_own_thread_transcripts.json"), ("p3_gpu_bound.txt", "gpu_bound_rate.txt"),
                       ("p3_lasso.json", "lasso.json"), ("p3_sumcheck.json", "sumcheck.json"), ("p3_extra.json", "extra.json"),
                       ("p3_configs.jsonl", "configs.jsonl")):
-        if os.path.exists(os.path.join("gpurun_out", src_)):
-            shutil.copy(os.path.join("gpurun_out", src_), "profiles/%s_%s" % (ROUND, dst))
+        if os.path.exists(os.path.join(SRC, src_)):
+            shutil.copy(os.path.join(SRC, src_), "profiles/%s_%s" % (ROUND, dst))
     for name in ("final_bench", "final_bench_b1", "final_bench_8x8", "final_bench_11x8", "final_bench_own_thread_transcripts"):
         pth = "profiles/%s_%s.json" % (ROUND, name)
         if not os.path.exists(pth):
@@ -155,4 +156,7 @@ def main():
 
 
 if __name__ == "__main__":
+    if len(sys.argv) != 2:
+        sys.exit("usage: python %s OUTDIR  (the directory the profile run wrote)" % sys.argv[0])
+    SRC = sys.argv[1]
     main()

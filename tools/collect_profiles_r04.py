@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Copies what tools/regen_profiles_r04.sh left under gpurun_out/p4_* into profiles/ (r04_ names) and derives, per kernel of ONE
-lone 2^20 proof, launches / time / HBM traffic / VALU instructions (profiles/r04_one_proof_kernels.json), the traffic record
+"""python tools/collect_profiles_r04.py OUTDIR: copies what tools/regen_profiles_r04.sh left in OUTDIR as p4_* into profiles/
+(r04_ names) and derives, per kernel of ONE lone 2^20 proof, launches / time / HBM traffic / VALU instructions (profiles/r04_one_proof_kernels.json), the traffic record
 bench.py reads for `roofline.traffic` (profiles/r04_traffic.json), and the HBM traffic of the MLE kernels of the per-kernel leg
-against their algorithmic bytes (profiles/r04_mle_traffic.json).  Run from the repo root after the gpurun calls have merged
-their output."""
+against their algorithmic bytes (profiles/r04_mle_traffic.json).  Run from the repo root once both parts of the
+profile run are in OUTDIR."""
 import collections
 import csv
 import glob
@@ -11,6 +11,7 @@ import json
 import os
 import re
 import shutil
+import sys
 
 ROUND = "r04"
 
@@ -57,8 +58,8 @@ def mle_traffic():
                 out[short(r["Kernel_Name"])].append(float(r["Counter_Value"]) * scale)
         return out
     try:
-        F = per_kernel(newest("gpurun_out/p4_kernels_FETCH/**/*counter_collection.csv"), "FETCH_SIZE", 2048)  # KB, halved on gfx950
-        W = per_kernel(newest("gpurun_out/p4_kernels_WRITE/**/*counter_collection.csv"), "WRITE_SIZE", 1024)
+        F = per_kernel(newest(SRC + "/p4_kernels_FETCH/**/*counter_collection.csv"), "FETCH_SIZE", 2048)  # KB, halved on gfx950
+        W = per_kernel(newest(SRC + "/p4_kernels_WRITE/**/*counter_collection.csv"), "WRITE_SIZE", 1024)
     except AssertionError:
         return
     N = 1 << 20
@@ -84,7 +85,7 @@ def mle_traffic():
 
 def main():
     mle_traffic()
-    one = newest("gpurun_out/p4_one/**/*kernel_trace.csv")
+    one = newest(SRC + "/p4_one/**/*kernel_trace.csv")
     rows = sorted(csv.DictReader(open(one)), key=lambda r: int(r["Start_Timestamp"]))
     starts = [i for i, r in enumerate(rows) if "k_runs_stage<true>" in r["Kernel_Name"]]
     build = []
@@ -103,9 +104,9 @@ def main():
         d = dur[short(r["Kernel_Name"])]
         d[0] += 1
         d[1] += (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
-    F = last_build(counters(newest("gpurun_out/p4_one_FETCH/**/*counter_collection.csv"), {"FETCH_SIZE"}))
-    W = last_build(counters(newest("gpurun_out/p4_one_WRITE/**/*counter_collection.csv"), {"WRITE_SIZE"}))
-    V = last_build(counters(newest("gpurun_out/p4_one_VALU/**/*counter_collection.csv"), {"SQ_INSTS_VALU", "SQ_ACTIVE_INST_VALU2"}))
+    F = last_build(counters(newest(SRC + "/p4_one_FETCH/**/*counter_collection.csv"), {"FETCH_SIZE"}))
+    W = last_build(counters(newest(SRC + "/p4_one_WRITE/**/*counter_collection.csv"), {"WRITE_SIZE"}))
+    V = last_build(counters(newest(SRC + "/p4_one_VALU/**/*counter_collection.csv"), {"SQ_INSTS_VALU", "SQ_ACTIVE_INST_VALU2"}))
     per = collections.defaultdict(lambda: {"launches": 0, "us": 0.0, "fetch_bytes": 0.0, "write_bytes": 0.0, "valu_wave_instr": 0.0,
                                            "valu2_wave_instr": 0.0})
     for k, (n, us) in dur.items():
@@ -118,7 +119,7 @@ def main():
         per[k]["valu_wave_instr"] += c.get("SQ_INSTS_VALU", 0.0)
         per[k]["valu2_wave_instr"] += c.get("SQ_ACTIVE_INST_VALU2", 0.0)
     # what the hashing kernels hashed in that proof: the bench trace at 2^20 (stats of the same build through the API)
-    stats_path = "gpurun_out/p4_one_stats.json"
+    stats_path = SRC + "/p4_one_stats.json"
     st = json.load(open(stats_path)) if os.path.exists(stats_path) else {}
     hashes = {"k_level_hash": st.get("list_hash_perms")}
     N = 1 << 20
@@ -168,11 +169,11 @@ def main():
             f, r["launches"], r["us"], r["hbm_bytes"] / 1e6,
             ("  (%.2f x algorithmic)" % r["traffic_ratio"]) if "traffic_ratio" in r else "",
             ("  valu2 %.2f" % r["valu2_share"]) if "valu2_share" in r else ""))
-    shutil.copy(newest("gpurun_out/p4_one_FETCH/**/*counter_collection.csv"), "profiles/%s_pmc_fetch_size.csv" % ROUND)
-    shutil.copy(newest("gpurun_out/p4_one_WRITE/**/*counter_collection.csv"), "profiles/%s_pmc_write_size.csv" % ROUND)
-    shutil.copy(newest("gpurun_out/p4_one_VALU/**/*counter_collection.csv"), "profiles/%s_pmc_valu.csv" % ROUND)
+    shutil.copy(newest(SRC + "/p4_one_FETCH/**/*counter_collection.csv"), "profiles/%s_pmc_fetch_size.csv" % ROUND)
+    shutil.copy(newest(SRC + "/p4_one_WRITE/**/*counter_collection.csv"), "profiles/%s_pmc_write_size.csv" % ROUND)
+    shutil.copy(newest(SRC + "/p4_one_VALU/**/*counter_collection.csv"), "profiles/%s_pmc_valu.csv" % ROUND)
     for tag in ("kernels", "b1", "bdef", "lasso", "sumcheck"):
-        shutil.copy(newest("gpurun_out/p4_%s/**/*kernel_stats.csv" % tag), "profiles/%s_%s_kernel_stats.csv" % (ROUND, tag))
+        shutil.copy(newest(SRC + "/p4_%s/**/*kernel_stats.csv" % tag), "profiles/%s_%s_kernel_stats.csv" % (ROUND, tag))
     for src_, dst in (("p4_kernels.json", "kernels.json"), ("p4_kernels_plain.json", "kernels_unprofiled.json"),
                       ("p4_bench.json", "final_bench.json"), ("p4_bench_b1.json", "final_bench_b1.json"),
                       ("p4_bench_ctx_per_lane.json", "final_bench_context_per_lane.json"),
@@ -186,8 +187,8 @@ def main():
                       ("p4_icache_corun.txt", "icache_corun.txt"), ("p4_bench_upload16.json", "bench_upload_16_byte_records.json"),
                       ("p4_bench_upload32.json", "bench_upload_32_byte_records.json"),
                       ("p4_bench_batch4.json", "bench_2p20_jobs_of_up_to_4.json")):
-        if os.path.exists(os.path.join("gpurun_out", src_)):
-            shutil.copy(os.path.join("gpurun_out", src_), "profiles/%s_%s" % (ROUND, dst))
+        if os.path.exists(os.path.join(SRC, src_)):
+            shutil.copy(os.path.join(SRC, src_), "profiles/%s_%s" % (ROUND, dst))
     if os.path.exists("profiles/%s_bdef_union.json" % ROUND) and os.path.exists("profiles/%s_bdef_bench.json" % ROUND):
         u = json.load(open("profiles/%s_bdef_union.json" % ROUND))["classes"]["level_hash"]
         b = json.loads(open("profiles/%s_bdef_bench.json" % ROUND).read().strip().splitlines()[-1])["roofline"]
@@ -206,4 +207,7 @@ def main():
 
 
 if __name__ == "__main__":
+    if len(sys.argv) != 2:
+        sys.exit("usage: python %s OUTDIR  (the directory the profile run wrote)" % sys.argv[0])
+    SRC = sys.argv[1]
     main()

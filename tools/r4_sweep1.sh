@@ -1,7 +1,7 @@
 #!/bin/bash
 # round-4 A/B: GPU slots per lane count, legacy form, the ends of the size sweep (phases)
 out=gpurun_out/r4c; mkdir -p $out
-run() { name=$1; shift; timeout -k 10 400 python bench.py --no-extras --no-cpu-baseline "$@" > $out/$name.json 2> $out/$name.err || echo "$name failed"; python - <<PY
+run() { name=$1; shift; timeout -k 10 400 python bench.py --full --no-extras --no-cpu-baseline "$@" > $out/$name.json 2> $out/$name.err || echo "$name failed"; python - <<PY
 import json
 try:
     d=json.load(open("$out/$name.json"))

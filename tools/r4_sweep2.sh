@@ -1,6 +1,6 @@
 #!/bin/bash
 out=gpurun_out/r4d; mkdir -p $out
-run() { name=$1; shift; timeout -k 10 400 python bench.py --no-extras --no-cpu-baseline "$@" > $out/$name.json 2> $out/$name.err || echo "$name failed"; python - <<PY
+run() { name=$1; shift; timeout -k 10 400 python bench.py --full --no-extras --no-cpu-baseline "$@" > $out/$name.json 2> $out/$name.err || echo "$name failed"; python - <<PY
 import json
 try:
     d=json.load(open("$out/$name.json"))
