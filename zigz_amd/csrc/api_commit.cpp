@@ -263,10 +263,7 @@ zigz_status build_trees(zigz_ctx *ctx, const uint32_t *d_vals, size_t val_stride
             t.upper = (uint8_t *)u;
         }
         b.t = t;
-        if (ctx->debug_skip != 2) {
-            launch_runs_structure(b, ctx->stream, R.n ? stamp(4, 0) : nullptr);
-            launch_cons_structure(b, ctx->stream, G.n ? stamp(4, 0) : nullptr);
-        }
+        if (ctx->debug_skip != 2) launch_structure(b, ctx->stream, ctx->debug_skip == 0, stamp(4, 0));
         if (GS.n && b.g_has_slabs) {  // only if the group was dropped: its small-domain members' levels 0 and 1 by table
             const ColMap gs = slab_map(GS);
             launch_keccak_small_l01(d_vals, val_stride, n_values, npad, t.slab, stride, GS, ctx->d_sd_tables, ctx->d_sd_fallbacks + 1,
@@ -284,7 +281,7 @@ zigz_status build_trees(zigz_ctx *ctx, const uint32_t *d_vals, size_t val_stride
                 expect = (R.n ? more(ctx->caps.r_last[l]) : 0) + (G.n ? more(ctx->caps.g_last[l]) * G.n : 0) +
                          (G.n && ctx->caps.last_dropped ? (size_t)G.n * (npad >> l) : 0);
             }
-            if (ctx->debug_skip != 1) launch_level_hash(b, l, ctx->stream, stamp(5, 0), expect);
+            if (ctx->debug_skip != 1) launch_level_hash(b, l, ctx->stream, stamp(5, 0), expect, ctx->debug_skip == 0);
             if (l == top) break;
             ColMap m{};  // the densely built columns that already have level l: D, and H from level 1
             for (size_t c = 0; c < ncols; c++) {
@@ -704,12 +701,9 @@ static zigz_status job_build_batch_arena(zigz_commit_job *job, const uint32_t *c
     for (unsigned z = 0; z < nz; z++) cs.p[z] = srcs[z];
     launch_gather_cols(cs, nz, nc, N, src_stride, (uint32_t *)(a0 + o_cols), stride, S, ctx->stream);
     launch_zero_counters(nullptr, R.n ? b.r_ctr : nullptr, G.n ? b.g_ctr : nullptr, ctx->stream, nz, S);
-    if (ctx->debug_skip != 2) {
-        launch_runs_structure(b, ctx->stream, nullptr);
-        launch_cons_structure(b, ctx->stream, nullptr);
-    }
+    if (ctx->debug_skip != 2) launch_structure(b, ctx->stream, ctx->debug_skip == 0);
     for (unsigned l = 0; l <= t.top; l++)
-        if (ctx->debug_skip != 1) launch_level_hash(b, l, ctx->stream, nullptr);
+        if (ctx->debug_skip != 1) launch_level_hash(b, l, ctx->stream, nullptr, 0, ctx->debug_skip == 0);
     if (height && ctx->debug_skip != 1) launch_merkle_top(t, t.top, height, nc, ctx->stream, nullptr);
     HIPCHK(ctx, hipGetLastError());
     job->tree = t;

@@ -327,8 +327,15 @@ inline void set_zstride(MerkleBuild &b, size_t zs, unsigned nz) {
 void launch_runs_structure(const MerkleBuild &b, hipStream_t s, const KTime *kt = nullptr);
 // G: the table passes of the levels 0..top and the keep / drop decision (top + 3 launches, no hashing)
 void launch_cons_structure(const MerkleBuild &b, hipStream_t s, const KTime *kt = nullptr);
-// level L (<= top) of the R and G columns: hashes the two lists (and, when the group was dropped, its columns densely)
-void launch_level_hash(const MerkleBuild &b, unsigned L, hipStream_t s, const KTime *kt = nullptr, size_t expect = 0);  // expect: entries the level is expected to hold (sizing only; 0: the lists' room)
+// All structure passes of a build (R and G).  fused: the FUSED schedule -- the probe (when it runs), A = full leaf insert +
+// runs stage 0, B = leaf pass + runs stage 1, k_cons_decide; the table passes of the levels >= 1 and the runs stages >= 2 then
+// ride in the level-hash launches, which must be given fused = true as well.  Otherwise (the measurement modes; every build
+// compiled with -DZK_STRUCT_SEPARATE) the two calls above, every pass a launch of its own.  kt spans all its launches.
+void launch_structure(const MerkleBuild &b, hipStream_t s, bool fused, const KTime *kt = nullptr);
+// level L (<= top) of the R and G columns: hashes the two lists (and, when the group was dropped, its columns densely); fused:
+// with the structure passes that ride in it (launch_structure)
+void launch_level_hash(const MerkleBuild &b, unsigned L, hipStream_t s, const KTime *kt = nullptr, size_t expect = 0,  // expect: entries the level is expected to hold (sizing only; 0: the lists' room)
+                       bool fused = false);
 // writes the copies / non-representatives of the levels 0..top (whole-tree comparisons, single trees that outlive the call)
 void launch_fill_virtual(const MerkleBuild &b, hipStream_t s);
 // from level `first_level` (at most 512 nodes per column, found through t) to the root, one workgroup per column; the levels

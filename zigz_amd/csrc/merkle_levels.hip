@@ -7,6 +7,9 @@
 //   k_cons_leaf_insert, k_cons_pass, k_cons_decide
 //                     G: per level a wave-deduplicated pass over a generation-tagged open-addressing table
 //   k_level_hash      one launch per level: the R list, the G list x columns, or the group's columns densely when dropped
+//   k_structure, k_level_hash_rides
+//                     the fused schedule (default): the same passes in two front launches and as extra workgroups of the
+//                     level-hash launches (see "the fused schedule" below; -DZK_STRUCT_SEPARATE: one launch per pass)
 //   k_merkle_top      256 nodes per column -> root, one workgroup per column, no re-arm pauses (a dependent chain)
 //   k_runs_fill_level, k_cons_fill_level   materialise the virtual nodes (tests, single trees)
 //
@@ -142,12 +145,14 @@ __device__ __forceinline__ int wave_scan_max(int v) {  // values >= -1
 // level r + 1 follow from those of level r by OR-ing bit pairs and compressing the even bits (one lane per 64-bit word, two
 // lanes' halves joined by a cross-lane read) -- a few hundred instructions for all levels, then the list entries.
 constexpr int RUNS_WAVES = TPB / 64;
+// (bx, y): the workgroup's segment group and hinted column -- blockIdx.x / .y of k_runs_stage, a range of blockIdx.x in the
+// fused structure launches
 template <bool STAGE0>
-__global__ __launch_bounds__(TPB) void k_runs_stage(MerkleBuild b, unsigned stage, unsigned seg_log2, unsigned rmax, unsigned nseg,
-                                                    size_t in_off /*bytes, stage >= 1*/, size_t out_off /*bytes, next stage or ~0*/) {
+__device__ __forceinline__ void runs_stage_wg(const MerkleBuild &b, unsigned bx, unsigned y, unsigned stage, unsigned seg_log2,
+                                              unsigned rmax, unsigned nseg, size_t in_off, size_t out_off) {
     ZK_PRIO_SMALL();
     const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned y = blockIdx.y, segi = blockIdx.x * RUNS_WAVES + wave;
+    const unsigned segi = bx * RUNS_WAVES + wave;
     if (segi >= nseg) return;  // (wave-uniform; the waves of a workgroup never meet)
     const unsigned seg = 1u << seg_log2, words = seg / 64;
     const unsigned l_in = stage * RUN_STAGE_LEVELS;
@@ -283,28 +288,51 @@ __global__ __launch_bounds__(TPB) void k_runs_stage(MerkleBuild b, unsigned stag
         }
     }
 }
+template <bool STAGE0>
+__global__ __launch_bounds__(TPB) void k_runs_stage(MerkleBuild b, unsigned stage, unsigned seg_log2, unsigned rmax, unsigned nseg,
+                                                    size_t in_off /*bytes, stage >= 1*/, size_t out_off /*bytes, next stage or ~0*/) {
+    runs_stage_wg<STAGE0>(b, blockIdx.x, blockIdx.y, stage, seg_log2, rmax, nseg, in_off, out_off);
+}
+
+// the shape of runs stage st of a build, and how many workgroups it takes per hinted column
+struct RunsStage {
+    unsigned stage, seg_log2, rmax, nseg, wgs;  // wgs == 0: no stage (no hinted columns, or none rides in this launch)
+    size_t in_off, out_off;
+};
+static unsigned runs_nstages(const MerkleBuild &b) {
+    unsigned nstages = 1;
+    while (nstages * RUN_STAGE_LEVELS < b.t.r_lists.top) nstages++;
+    return b.rcols.n ? nstages : 0;
+}
+static RunsStage runs_stage_shape(const MerkleBuild &b, unsigned st) {
+    RunsStage r{};
+    if (st >= runs_nstages(b)) return r;
+    const unsigned top = b.t.r_lists.top;
+    const size_t n_in = b.npad >> (st * RUN_STAGE_LEVELS);
+    const size_t seg = n_in < RUN_SEG ? n_in : RUN_SEG;
+    r.stage = st;
+    r.seg_log2 = log2u(seg);
+    r.rmax = top - st * RUN_STAGE_LEVELS < RUN_STAGE_LEVELS ? top - st * RUN_STAGE_LEVELS : RUN_STAGE_LEVELS;
+    r.nseg = (unsigned)(n_in / seg);
+    r.wgs = (r.nseg + RUNS_WAVES - 1) / RUNS_WAVES;
+    r.in_off = st ? stage_off(b.npad, b.rcols.n, st) : 0;
+    r.out_off = st + 1 < runs_nstages(b) ? stage_off(b.npad, b.rcols.n, st + 1) : ~(size_t)0;
+    return r;
+}
 
 void launch_runs_structure(const MerkleBuild &b, hipStream_t s, const KTime *kt) {
     if (b.rcols.n == 0) return;
-    const unsigned top = b.t.r_lists.top;
-    unsigned nstages = 1;
-    while (nstages * RUN_STAGE_LEVELS < top) nstages++;
+    const unsigned nstages = runs_nstages(b);
     for (unsigned st = 0; st < nstages; st++) {
-        const size_t n_in = b.npad >> (st * RUN_STAGE_LEVELS);
-        const size_t seg = n_in < RUN_SEG ? n_in : RUN_SEG;
-        const unsigned rmax = top - st * RUN_STAGE_LEVELS < RUN_STAGE_LEVELS ? top - st * RUN_STAGE_LEVELS : RUN_STAGE_LEVELS;
-        const bool has_next = st + 1 < nstages;
-        const size_t in_off = st ? stage_off(b.npad, b.rcols.n, st) : 0;
-        const size_t out_off = has_next ? stage_off(b.npad, b.rcols.n, st + 1) : ~(size_t)0;
-        const unsigned nseg = (unsigned)(n_in / seg);
-        const dim3 grid((nseg + RUNS_WAVES - 1) / RUNS_WAVES, b.rcols.n, b.t.nz ? b.t.nz : 1);
+        const RunsStage r = runs_stage_shape(b, st);
+        const dim3 grid(r.wgs, b.rcols.n, b.t.nz ? b.t.nz : 1);
         hipEvent_t e0 = kt && st == 0 ? kt->start : nullptr, e1 = kt && st + 1 == nstages ? kt->stop : nullptr;
         if (st == 0) {
-            if (e0 || e1) hipExtLaunchKernelGGL(k_runs_stage<true>, grid, dim3(TPB), 0, s, e0, e1, 0, b, st, log2u(seg), rmax, nseg, in_off, out_off);
-            else hipLaunchKernelGGL(k_runs_stage<true>, grid, dim3(TPB), 0, s, b, st, log2u(seg), rmax, nseg, in_off, out_off);
+            if (e0 || e1) hipExtLaunchKernelGGL(k_runs_stage<true>, grid, dim3(TPB), 0, s, e0, e1, 0, b, st, r.seg_log2, r.rmax, r.nseg, r.in_off, r.out_off);
+            else hipLaunchKernelGGL(k_runs_stage<true>, grid, dim3(TPB), 0, s, b, st, r.seg_log2, r.rmax, r.nseg, r.in_off, r.out_off);
         } else {
-            if (e0 || e1) hipExtLaunchKernelGGL(k_runs_stage<false>, grid, dim3(TPB), 0, s, e0, e1, 0, b, st, log2u(seg), rmax, nseg, in_off, out_off);
-            else hipLaunchKernelGGL(k_runs_stage<false>, grid, dim3(TPB), 0, s, b, st, log2u(seg), rmax, nseg, in_off, out_off);
+            if (e0 || e1) hipExtLaunchKernelGGL(k_runs_stage<false>, grid, dim3(TPB), 0, s, e0, e1, 0, b, st, r.seg_log2, r.rmax, r.nseg, r.in_off, r.out_off);
+            else hipLaunchKernelGGL(k_runs_stage<false>, grid, dim3(TPB), 0, s, b, st, r.seg_log2, r.rmax, r.nseg, r.in_off, r.out_off);
         }
     }
 }
@@ -442,13 +470,13 @@ __device__ __forceinline__ void cons_insert_level(const MerkleBuild &b, unsigned
 // returns at once when the probe has dropped the group.  Keys the probe inserted are found again by the full pass: they keep
 // the list slots they took.
 constexpr unsigned CONS_SAMPLE = 16;
-__global__ __launch_bounds__(CONS_TPB) void k_cons_leaf_insert(MerkleBuild b, int sample) {
+// bx: the workgroup's index in the pass (blockIdx.x of the pass's own launch); s_set: CONS_SET words of LDS
+__device__ __forceinline__ void cons_leaf_insert_wg(const MerkleBuild &b, int sample, unsigned bx, unsigned long long *s_set) {
     ZK_PRIO_SMALL();
-    __shared__ unsigned long long s_set[CONS_SET];
     if (!sample && b.g_ctr[8]) return;  // dropped by the probe
     for (unsigned i = threadIdx.x; i < CONS_SET; i += CONS_TPB) s_set[i] = 0;
     __syncthreads();
-    const size_t k = (size_t)blockIdx.x * CONS_TPB + threadIdx.x;
+    const size_t k = (size_t)bx * CONS_TPB + threadIdx.x;
     if (sample && ((k / 64) % CONS_SAMPLE) != 0) return;  // (wave-uniform; no barrier below)
     const unsigned lane = threadIdx.x & 63;
     const bool valid = k < b.npad;
@@ -456,17 +484,20 @@ __global__ __launch_bounds__(CONS_TPB) void k_cons_leaf_insert(MerkleBuild b, in
     const unsigned ld = wave_leader(key, valid, lane);
     cons_insert_level(b, s_set, 0, key, valid && ld == lane, (uint32_t)k, lane, k / 64);
 }
+__global__ __launch_bounds__(CONS_TPB) void k_cons_leaf_insert(MerkleBuild b, int sample) {
+    __shared__ unsigned long long s_set[CONS_SET];
+    cons_leaf_insert_wg(b, sample, blockIdx.x, s_set);
+}
 
 // Resolves level lr (every node learns the list slot of its representative) and, if do_insert, inserts the keys of level
 // lr + 1: node c / 2's key is the pair of the slots of c and c + 1, which sit in neighbouring lanes.
 template <bool LEAF>
-__global__ __launch_bounds__(CONS_TPB) void k_cons_pass(MerkleBuild b, unsigned lr, int do_insert) {
+__device__ __forceinline__ void cons_pass_wg(const MerkleBuild &b, unsigned lr, int do_insert, unsigned bx, unsigned long long *s_set) {
     ZK_PRIO_SMALL();
-    __shared__ unsigned long long s_set[CONS_SET];
     if (b.g_ctr[8]) return;  // the group was dropped (k_cons_decide)
     for (unsigned i = threadIdx.x; i < CONS_SET; i += CONS_TPB) s_set[i] = 0;
     __syncthreads();
-    const size_t n = b.npad >> lr, c = (size_t)blockIdx.x * CONS_TPB + threadIdx.x;
+    const size_t n = b.npad >> lr, c = (size_t)bx * CONS_TPB + threadIdx.x;
     const unsigned lane = threadIdx.x & 63;
     const bool valid = c < n;
     const size_t mask = 2 * b.npad - 1;
@@ -517,6 +548,11 @@ __global__ __launch_bounds__(CONS_TPB) void k_cons_pass(MerkleBuild b, unsigned 
         cons_insert_level(b, s_set, lr + 1, k2, mine && ld2 == lane, (uint32_t)(c >> 1), lane, c / 128);
     }
 }
+template <bool LEAF>
+__global__ __launch_bounds__(CONS_TPB) void k_cons_pass(MerkleBuild b, unsigned lr, int do_insert) {
+    __shared__ unsigned long long s_set[CONS_SET];
+    cons_pass_wg<LEAF>(b, lr, do_insert, blockIdx.x, s_set);
+}
 
 // keep or drop: a group whose leaves are mostly distinct does not repeat, and its table passes would find nothing.  After the
 // probe (sample != 0) the count is of the sampled leaves; after the full pass of all.
@@ -538,16 +574,18 @@ __global__ __launch_bounds__(64) void k_cons_decide(MerkleBuild b, int sample) {
     }
 }
 
+// the probe first (trees of >= 2^16 leaves: below that the whole insert costs less than a launch), then the full pass
+// -- unless the context's recent builds all kept their group (a service's slots see one kind of trace after the other): the
+// probe is then two launches that find out what is known; a trace that does not repeat after all is dropped by the full pass,
+// the expensive way, once
+static bool cons_probe(const MerkleBuild &b) { return b.npad >= ((size_t)1 << 16) && !b.g_no_probe; }
+
 void launch_cons_structure(const MerkleBuild &b, hipStream_t s, const KTime *kt) {
     if (b.gcols.n == 0) return;
     const unsigned top = b.t.g_lists.top;
     const unsigned nz = b.t.nz ? b.t.nz : 1;
     const dim3 g0((unsigned)((b.npad + CONS_TPB - 1) / CONS_TPB), 1, nz);
-    // the probe first (trees of >= 2^16 leaves: below that the whole insert costs less than a launch), then the full pass
-    // -- unless the context's recent builds all kept their group (a service's slots see one kind of trace after the other): the
-    // probe is then two launches that find out what is known; a trace that does not repeat after all is dropped by the full pass,
-    // the expensive way, once
-    const bool probe = b.npad >= ((size_t)1 << 16) && !b.g_no_probe;
+    const bool probe = cons_probe(b);
     if (probe) {
         if (kt) hipExtLaunchKernelGGL(k_cons_leaf_insert, g0, dim3(CONS_TPB), 0, s, kt->start, nullptr, 0, b, 1);
         else hipLaunchKernelGGL(k_cons_leaf_insert, g0, dim3(CONS_TPB), 0, s, b, 1);
@@ -574,8 +612,10 @@ void launch_cons_structure(const MerkleBuild &b, hipStream_t s, const KTime *kt)
 #ifndef ZK_LEVEL_HASH_MIN_WAVES
 #define ZK_LEVEL_HASH_MIN_WAVES 1  // (A/B: waves per SIMD the compiler must leave room for)
 #endif
+// (bx, nbx): the workgroup's index among the launch's hashing workgroups and their number (blockIdx.x / gridDim.x of
+// k_level_hash)
 template <bool LEAF, bool PAUSE>
-__global__ __launch_bounds__(TPB, ZK_LEVEL_HASH_MIN_WAVES) void k_level_hash(MerkleBuild b, unsigned L, ColMap gdense, int prio) {
+__device__ __forceinline__ void level_hash_wg(const MerkleBuild &b, unsigned L, const ColMap &gdense, int prio, unsigned bx, unsigned nbx) {
     __shared__ unsigned long long s_r[RUN_SUBS + 1], s_g[RUN_SUBS + 1];  // exclusive prefixes of the sub-list lengths
 #ifdef ZK_LEVEL_HASH_LDS_PAD  // (A/B: unused LDS per workgroup caps the workgroups per CU)
     __shared__ unsigned s_pad[ZK_LEVEL_HASH_LDS_PAD / 4];
@@ -613,7 +653,7 @@ __global__ __launch_bounds__(TPB, ZK_LEVEL_HASH_MIN_WAVES) void k_level_hash(Mer
     const unsigned gn = b.gcols.n;
     const size_t cR = uniform64(s_r[RUN_SUBS]), cG = uniform64(s_g[RUN_SUBS]) * gn,
                  cD = (dropped && b.g_has_slabs) ? (size_t)gdense.n * n_L : 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {  // nodes hashed by the whole build
+    if (bx == 0 && threadIdx.x == 0) {  // nodes hashed by the whole build
         if (cR) atomicAdd(&b.r_ctr[0], (unsigned long long)cR);
         if (cG) atomicAdd(&b.g_ctr[0], (unsigned long long)cG);
     }
@@ -625,7 +665,7 @@ __global__ __launch_bounds__(TPB, ZK_LEVEL_HASH_MIN_WAVES) void k_level_hash(Mer
     // floor(2^32 / group size); a group of ONE column: 2^32 does not fit, and 2^32 - 1 gives "the quotient or one short of it" too
     const unsigned g_magic = gn > 1 ? (unsigned)(0x100000000ull / gn) : 0xffffffffu;
 #pragma unroll 1
-    for (size_t e = (size_t)blockIdx.x * TPB + threadIdx.x; e < total; e += (size_t)gridDim.x * TPB) {
+    for (size_t e = (size_t)bx * TPB + threadIdx.x; e < total; e += (size_t)nbx * TPB) {
         size_t col, k;
         uint8_t *out;
         const uint8_t *in0 = nullptr, *in1 = nullptr;
@@ -693,8 +733,107 @@ __global__ __launch_bounds__(TPB, ZK_LEVEL_HASH_MIN_WAVES) void k_level_hash(Mer
         store_digest_at(out, d);
     }
 }
+template <bool LEAF, bool PAUSE>
+__global__ __launch_bounds__(TPB, ZK_LEVEL_HASH_MIN_WAVES) void k_level_hash(MerkleBuild b, unsigned L, ColMap gdense, int prio) {
+    level_hash_wg<LEAF, PAUSE>(b, L, gdense, prio, blockIdx.x, gridDim.x);
+}
 
-void launch_level_hash(const MerkleBuild &b, unsigned L, hipStream_t s, const KTime *kt, size_t expect) {
+// ------------------------------------------------------------------ the fused schedule
+// What each structure launch reads: the table pass of level l + 1 (k_cons_pass) the representatives of level l and the keys
+// of level l + 1, which pass l wrote; the hash of level L the lists of level L (filled by the insertion of pass L - 1) and the
+// representatives of level L - 1 (resolved by pass L - 1); runs stage s the output of stage s - 1.  Nothing of what the hash of
+// level L reads is written by pass L + 1 (the representatives of level L + 1, the keys, list and counters of level L + 2), and
+// the reverse holds too -- so pass L + 1 runs as extra workgroups of the hash launch of level L, and stream order still gives
+// every later launch what it reads.  A build's structure launches are then A = [runs stage 0][full leaf insert], B = [runs
+// stage 1][leaf pass], k_cons_decide (after the probe, when it runs), and everything else rides in the level-hash launches.
+// -DZK_STRUCT_SEPARATE: every pass a launch of its own (the A/B reference); the measurement modes (option debug_skip) use that
+// schedule too.
+#ifndef ZK_STRUCT_SEPARATE
+static_assert(CONS_TPB == TPB, "the fused structure launches share the 256-thread workgroups of the hash and runs kernels "
+                               "(build with -DZK_STRUCT_SEPARATE for another ZK_CONS_TPB)");
+// A (FIRST) / B: [rs.wgs workgroups per hinted column of the runs stage][the table pass].  Here the runs stage goes first: it
+// is the longer pole of A (stage 0, one HBM pass over the hinted columns) and a few dozen latency-bound workgroups in B (stage
+// 1), which would otherwise start only after the 4096 workgroups of the leaf pass had been dispatched.
+template <bool FIRST>
+__global__ __launch_bounds__(TPB) void k_structure(MerkleBuild b, unsigned nruns, RunsStage rs) {
+    __shared__ unsigned long long s_set[CONS_SET];
+    if (blockIdx.x < nruns) {
+        runs_stage_wg<FIRST>(b, blockIdx.x % rs.wgs, blockIdx.x / rs.wgs, rs.stage, rs.seg_log2, rs.rmax, rs.nseg, rs.in_off, rs.out_off);
+        return;
+    }
+    const unsigned w = blockIdx.x - nruns;
+    if (FIRST) cons_leaf_insert_wg(b, 0, w, s_set);
+    else cons_pass_wg<true>(b, 0u, b.t.g_lists.top >= 1 ? 1 : 0, w, s_set);
+}
+// H(L): [npass workgroups of the table pass of level L + 1][the runs stage that rides here][the hash of level L].  The pass
+// workgroups come first, so they are dispatched first; their LDS key set is the launch's dynamic LDS, which the big levels
+// leave unused anyway (ZK_LH_BIG_LDS): the hash path keeps its registers, LDS and occupancy.
+// STAGE: the launch carries a runs stage (only the leaf level does: at most three stages, RUN_MAX_LEAVES) -- the variants
+// without one keep the hash path's registers
+static_assert((RUN_NODE_BITS - 8 + RUN_STAGE_LEVELS - 1) / RUN_STAGE_LEVELS <= 3, "a runs stage would ride above level 0");
+template <bool LEAF, bool PAUSE, bool STAGE>
+__global__ __launch_bounds__(TPB, ZK_LEVEL_HASH_MIN_WAVES) void k_level_hash_rides(MerkleBuild b, unsigned L, ColMap gdense, int prio,
+                                                                                   unsigned npass, RunsStage rs) {
+    extern __shared__ unsigned long long s_dyn[];
+    if (blockIdx.x < npass) {
+        cons_pass_wg<false>(b, L + 1, L + 1 < b.t.g_lists.top ? 1 : 0, blockIdx.x, s_dyn);
+        return;
+    }
+    const unsigned w = blockIdx.x - npass, nrs = STAGE ? rs.wgs * b.rcols.n : 0;
+    if (STAGE && w < nrs) {
+        runs_stage_wg<false>(b, w % rs.wgs, w / rs.wgs, rs.stage, rs.seg_log2, rs.rmax, rs.nseg, rs.in_off, rs.out_off);
+        return;
+    }
+    level_hash_wg<LEAF, PAUSE>(b, L, gdense, prio, w - nrs, gridDim.x - npass - nrs);
+}
+#endif
+
+// launch with begin / end timestamps when either event is given
+#define ZK_LAUNCH_EV(e0, e1, kern, grid, block, lds, s, ...)                                                      \
+    do {                                                                                                          \
+        const hipEvent_t ev0_ = (e0), ev1_ = (e1);                                                                \
+        if (ev0_ || ev1_) hipExtLaunchKernelGGL(kern, grid, block, lds, s, ev0_, ev1_, 0, __VA_ARGS__);           \
+        else hipLaunchKernelGGL(kern, grid, block, lds, s, __VA_ARGS__);                                          \
+    } while (0)
+
+// the runs stage that rides in the hash launch of level L (wgs == 0: none).  Stages 0 and 1 go in A and B; stage s >= 2 reads
+// what stage s - 1 wrote and emits the levels from RUN_STAGE_LEVELS s + 1 on, whose hash launches (and the ones that read
+// them as children) come long after H(s - 2) -- the first launch after the one that carries stage s - 1 (B comes right
+// before H(0)).
+static RunsStage runs_stage_riding(const MerkleBuild &b, unsigned L) { return runs_stage_shape(b, L + 2); }
+
+void launch_structure(const MerkleBuild &b, hipStream_t s, bool fused, const KTime *kt) {
+#ifdef ZK_STRUCT_SEPARATE
+    fused = false;
+#endif
+    if (!fused) {  // one stamp over both: begin with the first launch, end with the last
+        KTime k0{kt ? kt->start : nullptr, nullptr}, k1{nullptr, kt ? kt->stop : nullptr};
+        if (!b.gcols.n) k0.stop = k1.stop;
+        if (!b.rcols.n) k1.start = k0.start;
+        launch_runs_structure(b, s, kt ? &k0 : nullptr);
+        launch_cons_structure(b, s, kt ? &k1 : nullptr);
+        return;
+    }
+#ifndef ZK_STRUCT_SEPARATE
+    const unsigned nz = b.t.nz ? b.t.nz : 1;
+    const unsigned ncons = b.gcols.n ? (unsigned)((b.npad + CONS_TPB - 1) / CONS_TPB) : 0;
+    const RunsStage r0 = runs_stage_shape(b, 0), r1 = runs_stage_shape(b, 1);
+    const unsigned nra = r0.wgs * b.rcols.n, nrb = r1.wgs * b.rcols.n, na = nra + ncons, nb = nrb + ncons;
+    if (!na) return;
+    hipEvent_t e0 = kt ? kt->start : nullptr;
+    const hipEvent_t stop = kt ? kt->stop : nullptr;
+    if (ncons && cons_probe(b)) {
+        ZK_LAUNCH_EV(e0, nullptr, k_cons_leaf_insert, dim3(ncons, 1, nz), dim3(CONS_TPB), 0, s, b, 1);
+        e0 = nullptr;
+        hipLaunchKernelGGL(k_cons_decide, dim3(1, 1, nz), dim3(64), 0, s, b, 1);
+    }
+    ZK_LAUNCH_EV(e0, nb || ncons ? nullptr : stop, k_structure<true>, dim3(na, 1, nz), dim3(TPB), 0, s, b, nra, r0);
+    if (nb) ZK_LAUNCH_EV(nullptr, ncons ? nullptr : stop, k_structure<false>, dim3(nb, 1, nz), dim3(TPB), 0, s, b, nrb, r1);
+    if (ncons) ZK_LAUNCH_EV(nullptr, stop, k_cons_decide, dim3(1, 1, nz), dim3(64), 0, s, b, 0);
+#endif
+}
+
+void launch_level_hash(const MerkleBuild &b, unsigned L, hipStream_t s, const KTime *kt, size_t expect, bool fused) {
     if (b.rcols.n == 0 && b.gcols.n == 0) return;
     // when the group was dropped its columns are hashed densely here -- except the small-domain members on the levels 0 and 1,
     // which come from the tables (launch_keccak_small_l01, guarded by the same flag)
@@ -741,6 +880,23 @@ void launch_level_hash(const MerkleBuild &b, unsigned L, hipStream_t s, const KT
 #define ZK_LH_BIG_LDS 28672
 #endif
     const unsigned lds = prio ? 0u : (unsigned)ZK_LH_BIG_LDS;
+#ifndef ZK_STRUCT_SEPARATE
+    // the fused schedule: the table pass of level L + 1 and the runs stage of this level ride along, in front of the hash grid
+    const unsigned npass = fused && b.gcols.n && L < b.t.g_lists.top ? (unsigned)(((b.npad >> (L + 1)) + CONS_TPB - 1) / CONS_TPB) : 0;
+    const RunsStage rs = fused ? runs_stage_riding(b, L) : RunsStage{};
+    const unsigned nride = npass + rs.wgs * b.rcols.n;
+    if (nride) {
+        const dim3 grid(nride + (unsigned)wgs, 1, nz);
+        const unsigned lds_r = npass && lds < CONS_SET * 8 ? CONS_SET * 8 : lds;  // (the pass's key set)
+        if (L == 0 && rs.wgs) ZK_LAUNCH(kt, (k_level_hash_rides<true, true, true>), grid, dim3(TPB), lds_r, s, b, L, gd, prio, npass, rs);
+        else if (L == 0) ZK_LAUNCH(kt, (k_level_hash_rides<true, true, false>), grid, dim3(TPB), lds_r, s, b, L, gd, prio, npass, rs);
+        else if (!pause) ZK_LAUNCH(kt, (k_level_hash_rides<false, false, false>), grid, dim3(TPB), lds_r, s, b, L, gd, prio, npass, rs);
+        else ZK_LAUNCH(kt, (k_level_hash_rides<false, true, false>), grid, dim3(TPB), lds_r, s, b, L, gd, prio, npass, rs);
+        return;
+    }
+#else
+    (void)fused;
+#endif
     if (L == 0) ZK_LAUNCH(kt, (k_level_hash<true, true>), dim3((unsigned)wgs, 1, nz), dim3(TPB), lds, s, b, L, gd, prio);
     else if (!pause) ZK_LAUNCH(kt, (k_level_hash<false, false>), dim3((unsigned)wgs, 1, nz), dim3(TPB), lds, s, b, L, gd, prio);
     else ZK_LAUNCH(kt, (k_level_hash<false, true>), dim3((unsigned)wgs, 1, nz), dim3(TPB), lds, s, b, L, gd, prio);
