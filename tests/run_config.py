@@ -6,7 +6,8 @@ Run one BASELINE config at full size on one GPU and check it:   
    --config 4  RV64IM mixed loop, 2^22
    --config 5  fibonacci guest semantics, 2^24 (needs ~60 GB of HBM and ~12 GB of host memory)
 Checks: Verifier.verify (host mirror) and the oracle's verifier accept; proof size formula; for `--check-cols k`
-columns the Merkle root / opened leaf / value are recomputed by the oracle from the host witness."""
+columns (a register first) the Merkle root / opened leaf / value are recomputed by the oracle from the host witness, and the
+root of pc by the deduplicating reference (tests/merkle_ref.py)."""
 import argparse
 import json
 import os
@@ -79,7 +80,15 @@ def main():
         cols = tr.witness()
         off = 32 + (324 + 8 * n_out) + (40 * nv + 8) + (4 + 24 * tr.num_lookups)
         rec = 68 + 41 * nv
-        for c in [0, 3, 41][: args.check_cols]:
+        # the sampled columns: first a register that changes in this program -- the first of the columns 2 .. 32 (x1 .. x31;
+        # run-aware, list-built) whose value changes more than 100 times -- then pc (content-addressed group) and mem.value;
+        # whatever k is, the root of pc is also checked against the deduplicating reference (a loop: a few thousand hashes),
+        # so that `--check-cols 1` sees one column of each structure-aware kind
+        import merkle_ref
+        assert merkle_ref.MerkleRef(cols[0]).root == proof[off: off + 32], "root of column 0"
+        reg = next(c for c in range(2, 33) if np.count_nonzero(cols[c][1:] != cols[c][:-1]) > 100)
+        out["checked_register_column"] = reg
+        for c in [reg, 0, 41][: args.check_cols]:
             r = proof[off + c * rec: off + (c + 1) * rec]
             lv, h = O.merkle_levels(cols[c])
             assert lv[(2 * N - 2) * 32:(2 * N - 1) * 32].tobytes() == r[:32], c

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from merkle_ref import _list_levels, _run_aware_hashed, _run_tile_nodes  # the numpy model of the run-aware leader rule
 
 pytestmark = pytest.mark.gpu
 
@@ -611,38 +612,6 @@ def test_unaligned_device_pointers(ctx):
     finally:
         ctx.dev_free(d)
         ctx.dev_free(o)
-
-
-def _run_tile_nodes(N, l):
-    """kernels.hpp run_tile_nodes: the nodes one segment of a stage covers at level l (its first node is always hashed)."""
-    if l == 0:
-        return 4096
-    s = (l - 1) // 6
-    n_in = N >> (6 * s)
-    return min(4096, n_in) >> (l - 6 * s)
-
-
-def _list_levels(nv):
-    """the list-driven levels of a 2^nv tree: 0 .. nv - 8 (down to 256 nodes per column)"""
-    return nv - 8 + 1
-
-
-def _run_aware_hashed(cols, levels):
-    """numpy model of k_runs_stage: nodes hashed (not copied from the left neighbour) on levels 0..levels-1; the first node
-    of every tile (what one segment of a stage covers at that level) is always hashed."""
-    total = 0
-    for col in np.asarray(cols):
-        uni = np.ones(col.size, dtype=bool)
-        for l in range(levels):
-            if l:
-                half = col[(1 << (l - 1))::(1 << l)]
-                uni = uni[0::2] & uni[1::2] & (col[::(1 << l)] == half)
-            val = col[::(1 << l)]
-            copy = np.zeros(val.size, dtype=bool)
-            copy[1:] = uni[1:] & uni[:-1] & (val[1:] == val[:-1])
-            copy[::_run_tile_nodes(col.size, l)] = False
-            total += int((~copy).sum())
-    return total
 
 
 def _tree_words(ctx, job, ncols):

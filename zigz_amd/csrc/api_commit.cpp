@@ -850,6 +850,11 @@ extern "C" zigz_status zigz_commit_roots(zigz_commit_job *job, uint8_t *roots) {
                     c.r[l] = (unsigned)(ru + ru / 4 + 64);
                 if (job->cons_hinted && !dropped && (g_over ? gu > c.g[l] : gu * 10 > (unsigned long long)c.g[l] * 8))
                     c.g[l] = (unsigned)(gu + gu / 4 + 64);
+                // A G list that ran out of room hides what the levels above it need: the nodes that found no slot share their
+                // sub-list's last one, so their parents' keys look alike and the level above counts too few.  Learning one level
+                // per build would take more builds than a job may repeat: give every level at least the room of the one below
+                // (the lists never get more than "every node hashed", cons_lists).
+                if (g_over && job->cons_hinted && !dropped && l > 0 && c.g[l] < c.g[l - 1]) c.g[l] = c.g[l - 1];
             }
             c.last_dropped = dropped;
             if (dropped) c.g_slabs = true;  // this context's traces do not repeat: give the group's columns slabs from now on

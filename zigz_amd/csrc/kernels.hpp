@@ -186,7 +186,8 @@ constexpr unsigned RUN_NODE_BITS = 26;    // R list entry = hinted-column index 
 constexpr size_t RUN_MIN_LEAVES = 32768;  // smaller trees are built densely
 constexpr size_t RUN_MAX_LEAVES = (size_t)1 << RUN_NODE_BITS;
 // counters of a build: word 0 = nodes hashed in all; word 8 (the group's array only) = "group dropped" flag, word 9 = distinct
-// leaves found; per level l and sub-list s the length at word (1 + l * RUN_SUBS + s) * 16
+// leaves found (leaf keys inserted, when a list of the build ran out of room), word 11 = leaves that took a slot of their own in the leaf pass (fingerprint collisions; many once any list has run
+// out of room: k_cons_decide takes them off its count); per level l and sub-list s the length at word (1 + l * RUN_SUBS + s) * 16
 constexpr unsigned RUN_CTRS = (1 + RUN_MAX_LEVELS * RUN_SUBS) * 16;
 // ... followed, in the R counters, by one word per hinted column: != 0 -> the column is NOT constant (k_runs_stage sets it when
 // a segment holds a change or starts with a value other than the column's first).  What the eval of a commit job skips (EvalSkip).

@@ -535,6 +535,10 @@ __device__ __forceinline__ void cons_pass_wg(const MerkleBuild &b, unsigned lr, 
     }
     if (valid && r == 0xffffffffu) alone = true;  // (cannot happen)
     const unsigned own = cons_take_slot(b, lr, alone, lane, c / 64);
+    if (LEAF) {  // word 11: the leaves that stand alone -- none but fingerprint collisions unless a list ran out of room (k_cons_decide)
+        const unsigned long long am = __ballot(alone);
+        if (am && lane == (unsigned)__builtin_ctzll(am)) atomicAdd(&b.g_ctr[11], (unsigned long long)__builtin_popcountll(am));
+    }
     if (alone) {
         r = own;
         b.g_list[b.t.g_lists.base[lr] + own] = (uint32_t)c;
@@ -567,6 +571,15 @@ __global__ __launch_bounds__(64) void k_cons_decide(MerkleBuild b, int sample) {
             b.g_ctr[8] = drop ? 1 : 0;
             b.g_ctr[9] = drop ? c * CONS_SAMPLE : 0;  // (distinct leaves: an estimate when the probe drops the group)
         } else if (!b.g_ctr[8]) {  // (a group the probe dropped stays dropped: the full pass did not run)
+            // ANY list of the build that ran out of room sets word 10, bit 0 (the level-1 insert that rides in the leaf pass
+            // too: the subtraction below then takes off true fingerprint collisions only, which is harmless).  A level-0 list out
+            // of room inflates the count: the tuples that found no slot share their sub-list's
+            // last one, and every leaf that resolves to it and finds another tuple's node there stands "alone" in a slot of its
+            // own -- a loop of a few thousand steps counts as millions of distinct leaves, was dropped as "does not repeat",
+            // the context learnt nothing and never content-addressed such a group.  The keys that were INSERTED are counted
+            // right whatever the room (the table always holds them): the count less the leaves that stood alone (word 11).
+            const bool out_of_room = (b.g_ctr[10] & 1) != 0;
+            if (out_of_room) c -= b.g_ctr[11] < c ? b.g_ctr[11] : c;
             b.g_ctr[9] = c;
             b.g_ctr[8] = c > b.npad / 4 ? 1 : 0;
         }
