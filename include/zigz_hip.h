@@ -178,6 +178,14 @@ zigz_status zigz_commit_roots(zigz_commit_job *job, uint8_t *roots);
  * dirs ncols*nv B (prover.zig:431 -> polynomial_commit.zig:86-115 -> merkle_tree.zig:324-360). */
 zigz_status zigz_commit_open_all(zigz_commit_job *job, const uint64_t *points, uint64_t *values,
                                  uint64_t *indices, uint64_t *leaves, uint8_t *siblings, uint8_t *dirs);
+/* k openings of the job's trees in shared launches: cols[j] in the job's column numbering (proof by proof for a batched job),
+ * indices[j] < 2^nv.  All paths have nv levels: opening j at siblings + j*nv*32, dirs + j*nv; leaf_values[j] is the column's
+ * cell at indices[j].  Valid once zigz_commit_roots has returned ZIGZ_OK for the job and until zigz_commit_end
+ * (ZIGZ_ERR_BAD_STATE otherwise); before or after zigz_commit_open_all, whose results it does not change.  Host outputs.
+ * k <= ZIGZ_VERIFY_BATCH_MAX; k == 0: ZIGZ_OK, nothing touched; cols[j] >= the job's columns: ZIGZ_ERR_INVALID_ARGUMENT,
+ * indices[j] >= 2^nv: ZIGZ_ERR_INDEX_OUT_OF_BOUNDS, the first such j to *bad_index (if non-NULL), nothing written. */
+zigz_status zigz_commit_open_many(zigz_commit_job *job, size_t k, const uint32_t *cols, const uint64_t *indices,
+                                  uint8_t *siblings, uint8_t *dirs, uint64_t *leaf_values, size_t *bad_index);
 /* diagnostic (tests): device address of the job's trees once built -- per column `bytes_per_column` = 2 * 2^nv nodes x 32 B
  * in the kernels' internal node form (level l at node offset 2N - 2(N >> l)); valid until zigz_commit_end.  Lets a test
  * compare two builds of the same columns node for node (dense vs table / run-aware / content-addressed levels).  Whole
@@ -483,6 +491,26 @@ zigz_status zigz_merkle_commit_batch(zigz_ctx *ctx, const uint64_t *const *value
  * tree by tree, tree i at offset sum_{j<i} heights[j]; leaf_values[k].  One launch, one hand-off. */
 zigz_status zigz_merkle_open_batch(zigz_ctx *ctx, const zigz_merkle_batch *b, const uint64_t *indices, uint8_t *siblings,
                                    uint8_t *dirs, uint64_t *leaf_values, size_t *bad_index);
+/* tree_{trees[j]}.open(indices[j]) for j < k (merkle_tree.zig:324-360): any number of openings per tree, in any order, (tree,
+ * index) pairs may repeat -- one launch per chunk of at most 32 MiB of results instead of one call per opening.  Outputs are
+ * packed opening by opening in the layout zigz_merkle_verify_batch reads: opening j's siblings (32 B each) and dirs at offset
+ * sum_{i<j} height(trees[i]); leaf_values[k]; roots (k * 32 B, may be NULL): the root of trees[j], so that the four arrays plus
+ * heights are a complete argument list of the verify entries; heights (k, may be NULL).  Every opening is byte-identical to
+ * zigz_merkle_open_batch's for that tree and index.  All checks run before anything is launched or written: k == 0 returns
+ * ZIGZ_OK and touches nothing; ZIGZ_ERR_INVALID_ARGUMENT for ctx or b NULL, a b of another context, k > ZIGZ_VERIFY_BATCH_MAX,
+ * trees or indices NULL, leaf_values NULL, siblings or dirs NULL unless every opening has height 0, trees[j] >= the batch's
+ * table count; ZIGZ_ERR_INDEX_OUT_OF_BOUNDS for indices[j] >= the number of values of that table (zigz_merkle_open_batch's
+ * rule); for the last two the first offending j goes to *bad_index (if non-NULL).  Leaves the hint options, zigz_kernel_stats,
+ * an active commit job and other open batches alone. */
+zigz_status zigz_merkle_open_many(zigz_ctx *ctx, const zigz_merkle_batch *b, size_t k, const uint32_t *trees,
+                                  const uint64_t *indices, uint8_t *siblings, uint8_t *dirs, uint64_t *leaf_values,
+                                  uint8_t *roots, size_t *heights, size_t *bad_index);
+/* the same with siblings / dirs / leaf_values / roots written to DEVICE memory (d_siblings and d_roots 16-byte aligned,
+ * d_leaf_values 8-byte aligned, else ZIGZ_ERR_INVALID_ARGUMENT); trees, indices and heights stay on the host.  Queues one
+ * launch on the context's stream and returns; what it wrote is what zigz_dev_merkle_verify_batch takes. */
+zigz_status zigz_dev_merkle_open_many(zigz_ctx *ctx, const zigz_merkle_batch *b, size_t k, const uint32_t *trees,
+                                      const uint64_t *indices, uint8_t *d_siblings, uint8_t *d_dirs,
+                                      uint64_t *d_leaf_values, uint8_t *d_roots, size_t *heights, size_t *bad_index);
 /* CommitmentScheme.open(poly_i, tree_i, point_i) for every tree (polynomial_commit.zig:86-115): table i must have 2^v values
  * (ZIGZ_ERR_LENGTH_NOT_POWER_OF_TWO otherwise); points are concatenated, heights[i] canonical coordinates each; values[i] =
  * eval(point_i) over the stored values, indices[i] = pointToIndex(point_i) (:178-183), then the path as above.  One eval

@@ -93,6 +93,7 @@ SIGNATURES = {
     "zigz_commit_begin_batch": (C.c_int32, [vp, C.POINTER(vp), C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(vp)]),
     "zigz_commit_roots": (C.c_int32, [vp, u8p]),
     "zigz_commit_open_all": (C.c_int32, [vp, u64p, u64p, u64p, u64p, u8p, u8p]),
+    "zigz_commit_open_many": (C.c_int32, [vp, C.c_size_t, u32p, u64p, u8p, u8p, u64p, szp]),
     "zigz_commit_job_tree": (C.c_int32, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
     "zigz_commit_end": (None, [vp]),
     "zigz_lasso_prove": (C.c_int32, [vp, u64p, C.c_size_t, u64p, C.c_size_t, C.c_size_t, C.c_size_t, szp, u64p, u64p,
@@ -147,6 +148,8 @@ SIGNATURES = {
     "zigz_dev_merkle_commit_batch": (C.c_int32, [vp, C.POINTER(vp), szp, C.c_size_t, u8p, szp, C.POINTER(vp), szp]),
     "zigz_merkle_commit_batch": (C.c_int32, [vp, C.POINTER(u64p), szp, C.c_size_t, u8p, szp, C.POINTER(vp), szp]),
     "zigz_merkle_open_batch": (C.c_int32, [vp, vp, u64p, u8p, u8p, u64p, szp]),
+    "zigz_merkle_open_many": (C.c_int32, [vp, vp, C.c_size_t, u32p, u64p, u8p, u8p, u64p, u8p, szp, szp]),
+    "zigz_dev_merkle_open_many": (C.c_int32, [vp, vp, C.c_size_t, u32p, u64p, vp, vp, vp, vp, szp, szp]),
     "zigz_commit_open_batch": (C.c_int32, [vp, vp, u64p, u64p, u64p, u8p, u8p, u64p, szp]),
     "zigz_merkle_batch_destroy": (None, [vp, vp]),
     "zigz_merkle_verify_batch": (C.c_int32, [vp, C.c_size_t, u8p, szp, u64p, u8p, u8p, u8p, szp, szp]),

@@ -229,6 +229,8 @@ extern "C" void zigz_ctx_destroy(zigz_ctx *ctx) {
     if (ctx->epoch_own) (void)hipEventDestroy(ctx->epoch_own);
     for (int i = 0; i < 2; i++)
         if (ctx->ev_verify[i]) (void)hipEventDestroy(ctx->ev_verify[i]);
+    if (ctx->ev_open) (void)hipEventDestroy(ctx->ev_open);
+    if (ctx->h_open) (void)hipHostFree(ctx->h_open);
     if (ctx->d_flush) (void)hipFree(ctx->d_flush);
     if (ctx->d_sd_tables) (void)hipFree(ctx->d_sd_tables);
     if (ctx->d_sd_fallbacks) (void)hipFree(ctx->d_sd_fallbacks);

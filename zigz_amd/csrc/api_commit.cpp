@@ -1038,6 +1038,75 @@ extern "C" zigz_status zigz_commit_open_all(zigz_commit_job *job, const uint64_t
     ZIGZ_NOTHROW_END(job->ctx)
 }
 
+// k openings of the job's trees in shared launches (kernels.hip: k_open_many), chunked through pinned memory like
+// zigz_merkle_open_many.  A batched job in arenas runs proof z's openings in grid plane z (TreeRef's pointers follow
+// blockIdx.z), so a chunk's descriptors are sorted by proof; each carries its opening's position in the chunk.
+extern "C" zigz_status zigz_commit_open_many(zigz_commit_job *job, size_t k, const uint32_t *cols, const uint64_t *indices,
+                                             uint8_t *siblings, uint8_t *dirs, uint64_t *leaf_values, size_t *bad_index) {
+    if (job) ZIGZ_ENTER(job->ctx);
+    if (!job) return ZIGZ_ERR_INVALID_ARGUMENT;
+    zigz_ctx *ctx = job->ctx;
+    if (job->state != 1 && job->state != 2) return ZIGZ_ERR_BAD_STATE;
+    if (k == 0) return ZIGZ_OK;
+    size_t bad = 0;
+    switch (mo::check_openings(k, cols, indices, job->ncols, nullptr, job->N, &bad)) {
+    case mo::OK: break;
+    case mo::BAD_ARGUMENT: return ZIGZ_ERR_INVALID_ARGUMENT;
+    case mo::BAD_TREE:
+        set_err(ctx, "opening %zu names column %u of a job of %zu", bad, cols[bad], job->ncols);
+        return fail_at(bad_index, bad, ZIGZ_ERR_INVALID_ARGUMENT);
+    case mo::BAD_INDEX: return fail_at(bad_index, bad, ZIGZ_ERR_INDEX_OUT_OF_BOUNDS);
+    }
+    const size_t nv = job->nv;
+    if (!leaf_values || (nv && (!siblings || !dirs))) return ZIGZ_ERR_INVALID_ARGUMENT;
+    ZIGZ_NOTHROW_BEGIN
+    std::vector<uint64_t> off(k + 1);
+    for (size_t j = 0; j <= k; j++) off[j] = j * nv;
+    const std::vector<mo::Chunk> chunks = mo::plan_chunks(off, k, OPEN_CHUNK_BYTES, false);
+    const unsigned nz = job->zstride ? job->nz : 1;
+    const size_t ncols1 = job->zstride ? job->ncols1 : job->ncols;
+    size_t most = 0, most_n = 0;
+    for (const mo::Chunk &c : chunks) {
+        most = std::max(most, c.bytes);
+        most_n = std::max(most_n, c.hi - c.lo);
+    }
+    uint8_t *pin;
+    CHK(pinned(ctx, (chunks.size() > 1 ? 2 : 1) * most, &pin));
+    void *ws;
+    CHK(ws_get(ctx, WS_OPEN, most_n * sizeof(mo::Desc), &ws));
+    auto launch = [&](size_t ci, DoneFlag *done) -> zigz_status {
+        const mo::Chunk &c = chunks[ci];
+        uint8_t *st = pin + (ci & 1) * most;
+        const size_t n = c.hi - c.lo;
+        OpenManyZ zf{};  // counting sort by proof: first[z + 1] counts, then starts
+        for (size_t j = c.lo; j < c.hi; j++) zf.first[cols[j] / ncols1 + 1]++;
+        for (unsigned z = 0; z < nz; z++) zf.first[z + 1] += zf.first[z];
+        uint32_t next[BATCH_MAX];
+        memcpy(next, zf.first, sizeof(next));
+        mo::Desc *hd = (mo::Desc *)st;
+        for (size_t j = c.lo; j < c.hi; j++)
+            hd[next[cols[j] / ncols1]++] = mo::Desc{indices[j], (uint32_t)(cols[j] % ncols1), (uint32_t)(j - c.lo)};
+        // (the previous chunk's launch reads the descriptors: the copy queues behind it on the stream)
+        HIPCHK(ctx, hipMemcpyAsync(ws, st, n * sizeof(mo::Desc), hipMemcpyHostToDevice, ctx->stream));
+        *done = done_flag(ctx, 3 + (int)(ci & 1));
+        launch_open_many(job->tree, (unsigned)nv, job->d_cols, job->col_stride, (const mo::Desc *)ws, zf, nz, st + c.off_sib,
+                         st + c.off_dirs, (uint64_t *)(st + c.off_leaf), ctx->stream, *done);
+        HIPCHK(ctx, hipGetLastError());
+        return ZIGZ_OK;
+    };
+    auto take = [&](size_t ci) {
+        const mo::Chunk &c = chunks[ci];
+        const uint8_t *st = pin + (ci & 1) * most;
+        if (c.slots) {
+            memcpy(siblings + 32 * c.slot0, st + c.off_sib, 32 * c.slots);
+            memcpy(dirs + c.slot0, st + c.off_dirs, c.slots);
+        }
+        memcpy(leaf_values + c.lo, st + c.off_leaf, 8 * (c.hi - c.lo));
+    };
+    return run_open_chunks(ctx, chunks.size(), launch, take);
+    ZIGZ_NOTHROW_END(ctx)
+}
+
 extern "C" zigz_status zigz_commit_job_tree(zigz_commit_job *job, const void **d_tree, size_t *bytes_per_column) {
     if (job) ZIGZ_ENTER(job->ctx);
     if (!job || !d_tree || !bytes_per_column) return ZIGZ_ERR_INVALID_ARGUMENT;

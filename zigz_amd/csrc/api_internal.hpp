@@ -24,7 +24,7 @@
 using namespace zk;
 
 // ------------------------------------------------------------------ context
-enum { WS_IN64 = 0, WS_IN32, WS_OUT32, WS_OUT64, WS_SCRATCH, WS_TREE, WS_FOLD, WS_MISC, WS_COLS, WS_LASSO, WS_DEDUP, WS_WITNESS, WS_RUNS, WS_RUNMETA, WS_CONS, WS_CONSMETA, WS_BATCH, WS_SCBATCH, WS_SCBATCH_IN, WS_VERIFY, WS_SLOTS };
+enum { WS_IN64 = 0, WS_IN32, WS_OUT32, WS_OUT64, WS_SCRATCH, WS_TREE, WS_FOLD, WS_MISC, WS_COLS, WS_LASSO, WS_DEDUP, WS_WITNESS, WS_RUNS, WS_RUNMETA, WS_CONS, WS_CONSMETA, WS_BATCH, WS_SCBATCH, WS_SCBATCH_IN, WS_VERIFY, WS_OPEN, WS_SLOTS };
 
 constexpr int KEV_MAX = 72;
 struct ListCaps {
@@ -102,6 +102,9 @@ struct zigz_ctx {
     size_t h_batch_bytes;
     hipEvent_t ev_verify[2];  // the batched verify's host form: the upload from each half of its pinned staging (created on first use)
     int verify_pause;         // option "verify_pause": 0 = by launch size, 1 = always, 2 = never (A/B)
+    uint8_t *h_open;          // pinned descriptor staging of zigz_dev_merkle_open_many, which returns while its upload may still
+    size_t h_open_bytes;      // be in flight: its own region, not reused before ev_open (recorded behind the upload) has passed
+    hipEvent_t ev_open;
 };
 static const size_t FLUSH_BYTES = (size_t)1 << 30;
 static const size_t SUMS_SLOTS = 8192;  // [0, 4096): results of the API calls; [4096, 8192): scratch of the measurement hook
@@ -190,3 +193,25 @@ zigz_status build_trees(zigz_ctx *ctx, const uint32_t *d_vals, size_t val_stride
 zigz_status keccak_times_collect(zigz_ctx *ctx);
 extern std::atomic<int> g_sleep_wait;
 #pragma GCC visibility pop
+
+constexpr size_t OPEN_CHUNK_BYTES = (size_t)32 << 20;  // staging per chunk of the many-openings host forms
+// The chunked hand-off of the many-openings host forms: launch(ci, &done) stages and queues chunk ci, whose kernel writes into
+// half ci & 1 of a pinned region and signals `done` (words 3 and 4 of the completion words, one per half); take(ci) copies the
+// finished chunk to the caller while chunk ci + 1 runs.  A half is staged again only after take() has emptied it.
+template <class Launch, class Take>
+zigz_status run_open_chunks(zigz_ctx *ctx, size_t n, Launch launch, Take take) {
+    DoneFlag done[2];
+    if (n) CHK(launch((size_t)0, &done[0]));
+    for (size_t ci = 0; ci < n; ci++) {
+        if (ci + 1 < n) CHK(launch(ci + 1, &done[(ci + 1) & 1]));
+        // a chunk can outlast one round of polling; the runtime's own wait would also wait for the chunk behind it, so ask
+        // it only whether the stream has ended (or faulted) in between
+        bool seen = false;
+        while (!ctx->timing && !(seen = g_sleep_wait.load() ? sleep_wait(done[ci & 1].flag, done[ci & 1].seq)
+                                                            : spin_wait(done[ci & 1].flag, done[ci & 1].seq)))
+            if (hipStreamQuery(ctx->stream) != hipErrorNotReady) break;
+        if (!seen) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        take(ci);
+    }
+    return ZIGZ_OK;
+}

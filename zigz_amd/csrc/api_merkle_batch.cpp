@@ -351,6 +351,142 @@ extern "C" zigz_status zigz_commit_open_batch(zigz_ctx *ctx, const zigz_merkle_b
     ZIGZ_NOTHROW_END(ctx)
 }
 
+// ---- many openings per tree (merkle_batch.hip: k_mbatch_open_many)
+namespace {
+
+// the descriptors of openings [c.lo, c.hi) into hd
+void fill_descs(const mo::Chunk &c, const uint32_t *trees, const uint64_t *indices, const std::vector<uint64_t> &off, mo::Desc *hd) {
+    for (size_t j = c.lo; j < c.hi; j++) hd[j - c.lo] = mo::Desc{indices[j], trees[j], (uint32_t)(off[j] - c.slot0)};
+}
+void fill_trees(const zigz_merkle_batch *b, MOpenTree *ht) {
+    for (size_t i = 0; i < b->k; i++)
+        ht[i] = MOpenTree{b->d_tree + b->tree_off[i] * 32, b->d_vals + b->vals_off[i], b->npad[i], b->height[i], 0};
+}
+
+// Host form: every chunk's siblings, directions, leaves and roots are written by the kernel into one half of a pinned region
+// and copied to the caller while the next chunk runs.  A half: tree table (chunk 0 only) | descriptors | outputs.
+zigz_status open_many_host(zigz_ctx *ctx, const zigz_merkle_batch *b, const uint32_t *trees, const uint64_t *indices,
+                           const std::vector<uint64_t> &off, size_t k, uint8_t *siblings, uint8_t *dirs, uint64_t *leaf_values,
+                           uint8_t *roots) {
+    const std::vector<mo::Chunk> chunks = mo::plan_chunks(off, k, OPEN_CHUNK_BYTES, roots != nullptr);
+    const size_t tabs_bytes = align256(b->k * sizeof(MOpenTree));
+    size_t most = 0, most_n = 0;
+    for (const mo::Chunk &c : chunks) {
+        most = std::max(most, c.bytes);
+        most_n = std::max(most_n, c.hi - c.lo);
+    }
+    const size_t half_bytes = tabs_bytes + most;
+    uint8_t *pin;
+    CHK(pinned(ctx, (chunks.size() > 1 ? 2 : 1) * half_bytes, &pin));
+    void *ws;
+    CHK(ws_get(ctx, WS_OPEN, tabs_bytes + most_n * sizeof(mo::Desc), &ws));
+    const MOpenTree *d_trees = (const MOpenTree *)ws;
+    mo::Desc *d_desc = (mo::Desc *)((uint8_t *)ws + tabs_bytes);
+    auto launch = [&](size_t ci, DoneFlag *done) -> zigz_status {
+        const mo::Chunk &c = chunks[ci];
+        uint8_t *h = pin + (ci & 1) * half_bytes, *st = h + tabs_bytes;
+        const size_t n = c.hi - c.lo;
+        fill_descs(c, trees, indices, off, (mo::Desc *)st);
+        if (ci == 0) {  // the tree table rides in front of the first chunk's descriptors: one copy per chunk
+            fill_trees(b, (MOpenTree *)h);
+            HIPCHK(ctx, hipMemcpyAsync(ws, h, tabs_bytes + n * sizeof(mo::Desc), hipMemcpyHostToDevice, ctx->stream));
+        } else {  // (the previous chunk's launch reads d_desc: the copy queues behind it on the stream)
+            HIPCHK(ctx, hipMemcpyAsync(d_desc, st, n * sizeof(mo::Desc), hipMemcpyHostToDevice, ctx->stream));
+        }
+        const MOpenOut o{st + c.off_sib, st + c.off_dirs, (uint64_t *)(st + c.off_leaf), roots ? st + c.off_roots : nullptr};
+        *done = done_flag(ctx, 3 + (int)(ci & 1));
+        launch_mbatch_open_many(d_trees, d_desc, (unsigned)n, (unsigned)c.slots, c.zero_height, o, false, ctx->stream, *done);
+        HIPCHK(ctx, hipGetLastError());
+        return ZIGZ_OK;
+    };
+    auto take = [&](size_t ci) {
+        const mo::Chunk &c = chunks[ci];
+        const uint8_t *st = pin + (ci & 1) * half_bytes + tabs_bytes;
+        const size_t n = c.hi - c.lo;
+        if (c.slots) {
+            memcpy(siblings + 32 * c.slot0, st + c.off_sib, 32 * c.slots);
+            memcpy(dirs + c.slot0, st + c.off_dirs, c.slots);
+        }
+        memcpy(leaf_values + c.lo, st + c.off_leaf, 8 * n);
+        if (roots) memcpy(roots + 32 * c.lo, st + c.off_roots, 32 * n);
+    };
+    return run_open_chunks(ctx, chunks.size(), launch, take);
+}
+
+// Device form: one launch writes the caller's device arrays; only the tree table and the descriptors go up, from a pinned
+// region of their own that the next call does not touch before this call's upload has left it.
+zigz_status open_many_dev(zigz_ctx *ctx, const zigz_merkle_batch *b, const uint32_t *trees, const uint64_t *indices,
+                          const std::vector<uint64_t> &off, size_t k, uint8_t *d_siblings, uint8_t *d_dirs, uint64_t *d_leaf_values,
+                          uint8_t *d_roots) {
+    const size_t tabs_bytes = align256(b->k * sizeof(MOpenTree)), up_bytes = tabs_bytes + k * sizeof(mo::Desc);
+    if (!ctx->ev_open) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_open, hipEventDisableTiming));
+    else HIPCHK(ctx, hipEventSynchronize(ctx->ev_open));
+    if (ctx->h_open_bytes < up_bytes) {
+        if (ctx->h_open) (void)hipHostFree(ctx->h_open);
+        ctx->h_open = nullptr;
+        ctx->h_open_bytes = 0;
+        const size_t want = align256(up_bytes + up_bytes / 8);
+        HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_open, want, hipHostMallocDefault));
+        ctx->h_open_bytes = want;
+    }
+    void *ws;
+    CHK(ws_get(ctx, WS_OPEN, up_bytes, &ws));
+    mo::Chunk c{};
+    c.hi = k;
+    bool zero_height = false;
+    for (size_t j = 0; j < k && !zero_height; j++) zero_height = off[j + 1] == off[j];
+    fill_trees(b, (MOpenTree *)ctx->h_open);
+    fill_descs(c, trees, indices, off, (mo::Desc *)(ctx->h_open + tabs_bytes));
+    HIPCHK(ctx, hipMemcpyAsync(ws, ctx->h_open, up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev_open, ctx->stream));
+    const MOpenOut o{d_siblings, d_dirs, d_leaf_values, d_roots};
+    launch_mbatch_open_many((const MOpenTree *)ws, (const mo::Desc *)((uint8_t *)ws + tabs_bytes), (unsigned)k, (unsigned)off[k],
+                            zero_height, o, true, ctx->stream, DoneFlag());
+    HIPCHK(ctx, hipGetLastError());
+    return ZIGZ_OK;
+}
+
+zigz_status open_many(zigz_ctx *ctx, const zigz_merkle_batch *b, bool dev, size_t k, const uint32_t *trees, const uint64_t *indices,
+                      uint8_t *siblings, uint8_t *dirs, uint64_t *leaf_values, uint8_t *roots, size_t *heights, size_t *bad_index) {
+    ZIGZ_ENTER(ctx);
+    if (!ctx || !b || b->ctx != ctx) return ZIGZ_ERR_INVALID_ARGUMENT;
+    if (k == 0) return ZIGZ_OK;
+    if (dev && (((uintptr_t)siblings | (uintptr_t)roots) & 15 || (uintptr_t)leaf_values & 7)) return ZIGZ_ERR_INVALID_ARGUMENT;
+    size_t bad = 0;
+    switch (mo::check_openings(k, trees, indices, b->k, b->n.data(), 0, &bad)) {
+    case mo::OK: break;
+    case mo::BAD_ARGUMENT: return ZIGZ_ERR_INVALID_ARGUMENT;
+    case mo::BAD_TREE:
+        set_err(ctx, "opening %zu names tree %u of a batch of %zu", bad, trees[bad], b->k);
+        return fail_at(bad_index, bad, ZIGZ_ERR_INVALID_ARGUMENT);
+    case mo::BAD_INDEX: return fail_at(bad_index, bad, ZIGZ_ERR_INDEX_OUT_OF_BOUNDS);  // merkle_tree.zig:325 (values.len)
+    }
+    ZIGZ_NOTHROW_BEGIN
+    std::vector<uint64_t> off;
+    mo::offsets(k, trees, b->height.data(), off);
+    if (!leaf_values || (off[k] && (!siblings || !dirs))) return ZIGZ_ERR_INVALID_ARGUMENT;
+    CHK(dev ? open_many_dev(ctx, b, trees, indices, off, k, siblings, dirs, leaf_values, roots)
+            : open_many_host(ctx, b, trees, indices, off, k, siblings, dirs, leaf_values, roots));
+    if (heights)
+        for (size_t j = 0; j < k; j++) heights[j] = b->height[trees[j]];
+    return ZIGZ_OK;
+    ZIGZ_NOTHROW_END(ctx)
+}
+
+}  // namespace
+
+extern "C" zigz_status zigz_merkle_open_many(zigz_ctx *ctx, const zigz_merkle_batch *b, size_t k, const uint32_t *trees,
+                                             const uint64_t *indices, uint8_t *siblings, uint8_t *dirs, uint64_t *leaf_values,
+                                             uint8_t *roots, size_t *heights, size_t *bad_index) {
+    return open_many(ctx, b, false, k, trees, indices, siblings, dirs, leaf_values, roots, heights, bad_index);
+}
+
+extern "C" zigz_status zigz_dev_merkle_open_many(zigz_ctx *ctx, const zigz_merkle_batch *b, size_t k, const uint32_t *trees,
+                                                 const uint64_t *indices, uint8_t *d_siblings, uint8_t *d_dirs,
+                                                 uint64_t *d_leaf_values, uint8_t *d_roots, size_t *heights, size_t *bad_index) {
+    return open_many(ctx, b, true, k, trees, indices, d_siblings, d_dirs, d_leaf_values, d_roots, heights, bad_index);
+}
+
 extern "C" void zigz_merkle_batch_destroy(zigz_ctx *ctx, zigz_merkle_batch *b) {
     ZIGZ_ENTER(ctx);
     batch_free(ctx ? ctx : (b ? b->ctx : nullptr), b);

@@ -1076,6 +1076,58 @@ void launch_paths(const TreeRef &t, size_t n_values, unsigned height, const uint
     hipLaunchKernelGGL(k_paths, dim3((unsigned)ncols, 1, t.nz ? t.nz : 1), dim3(64), 0, s, t, n_values, height, d_vals, val_stride, d_idx,
                        d_sib, d_dirs, d_leaf, done);
 }
+// Many openings of a job's trees (zigz_commit_open_many).  The work item is 16 bytes of one sibling digest, numbered along the
+// proof's descriptors: item = (descriptor e, level l, half); all paths have nv levels, so consecutive lanes store consecutive
+// 16 bytes of an opening's path.  Every sibling resolves through node_ptr exactly as in k_paths, virtual leaves included (both
+// lanes of such a digest hash the value: the wave walks the permutation once either way).  A job of height 0 has no sibling
+// lanes: one thread per opening writes the leaf value.
+__global__ __launch_bounds__(TPB) void k_open_many(TreeRef t, unsigned nv, size_t n_values, const uint32_t *__restrict__ vals,
+                                                   size_t val_stride, const mo::Desc *__restrict__ desc, OpenManyZ zf,
+                                                   uint8_t *__restrict__ sib, uint8_t *__restrict__ dirs,
+                                                   uint64_t *__restrict__ leaf, DoneFlag done) {
+    ZK_PRIO_SMALL();
+    const unsigned z = blockIdx.z, first = zf.first[z], cnt = zf.first[z + 1] - first;
+    if (t.zstride) vals += (size_t)z * (t.zstride / 4);  // a batched job: proof z's columns
+    const unsigned item = blockIdx.x * TPB + threadIdx.x;
+    if (nv == 0) {
+        if (item < cnt) {
+            const mo::Desc d = desc[first + item];
+            leaf[d.off] = vals[(size_t)d.tree * val_stride + d.index];
+        }
+    } else if (item < cnt * 2 * nv) {
+        const unsigned e = item / (2 * nv), r = item - e * 2 * nv, l = r >> 1, half = r & 1;
+        const mo::Desc d = desc[first + e];
+        const size_t col = d.tree;
+        const size_t ci = d.index >> l, node = ci ^ 1;
+        bool virt_leaf = l == 0 && col < 64 && ((t.virtual_leaves >> col) & 1);  // leaf digests of this column were never written
+        if (l == 0 && col < 64 && ((t.g_sd_mask >> col) & 1) && *t.g_dropped) virt_leaf = true;
+        uint4 v;
+        if (virt_leaf) {
+            const Digest g = sha3_leaf<false>(node < n_values ? (uint64_t)vals[col * val_stride + node] : 0);
+            const uint64_t a = canonical_word(half ? g.w[2] : g.w[0]), b = canonical_word(half ? g.w[3] : g.w[1]);
+            v = make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
+        } else {
+            v = canonical_half(node_ptr(t, col, l, node) + half * 16);
+        }
+        const size_t slot = (size_t)d.off * nv + l;
+        *reinterpret_cast<uint4 *>(sib + slot * 32 + half * 16) = v;
+        if (!half) {
+            dirs[slot] = (uint8_t)(ci & 1);  // directions[l] = is_right
+            if (l == 0) leaf[d.off] = vals[col * val_stride + d.index];
+        }
+    }
+    signal_done_block(done, gridDim.x * gridDim.z);
+}
+void launch_open_many(const TreeRef &t, unsigned nv, const uint32_t *d_vals, size_t val_stride, const mo::Desc *d_desc,
+                      const OpenManyZ &zf, unsigned nz, uint8_t *d_sib, uint8_t *d_dirs, uint64_t *d_leaf, hipStream_t s,
+                      DoneFlag done) {
+    unsigned most = 0;
+    for (unsigned z = 0; z < nz; z++)
+        if (zf.first[z + 1] - zf.first[z] > most) most = zf.first[z + 1] - zf.first[z];
+    const size_t items = (size_t)most * (nv ? 2 * nv : 1);
+    hipLaunchKernelGGL(k_open_many, dim3((unsigned)((items + TPB - 1) / TPB), 1, nz), dim3(TPB), 0, s, t, nv, t.npad, d_vals,
+                       val_stride, d_desc, zf, d_sib, d_dirs, d_leaf, done);
+}
 TreeRef slab_tree_ref(uint8_t *d_tree, size_t npad) {
     TreeRef t{};
     t.npad = npad;

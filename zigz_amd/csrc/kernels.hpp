@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "open_plan.hpp"
+
 namespace zk {
 
 // Optional kernel-exact timing of one launch: both events are stamped with the dispatch's own begin / end timestamps
@@ -384,6 +386,15 @@ void launch_publish_u32(const uint32_t *d_src, size_t n, uint32_t *h_dst, hipStr
 void launch_paths(const TreeRef &t, size_t n_values, unsigned height, const uint32_t *d_vals, size_t val_stride,
                   const uint64_t *d_idx, uint8_t *d_sib, uint8_t *d_dirs, uint32_t *d_leaf, size_t ncols, hipStream_t s,
                   DoneFlag done = DoneFlag());
+// Many openings of a commit job's trees (zigz_commit_open_many): descriptor e of proof z (descriptors zf.first[z] ..
+// zf.first[z + 1], grid z = proof) opens column `tree` of that proof at `index`; its nv siblings go to slot off * nv of d_sib /
+// d_dirs, its leaf value to d_leaf[off].  Digests are found through node_ptr like K7's; same output-major lanes as above.
+struct OpenManyZ {
+    uint32_t first[33];
+};
+void launch_open_many(const TreeRef &t, unsigned nv, const uint32_t *d_vals, size_t val_stride, const mo::Desc *d_desc,
+                      const OpenManyZ &zf, unsigned nz, uint8_t *d_sib, uint8_t *d_dirs, uint64_t *d_leaf, hipStream_t s,
+                      DoneFlag done);
 // a TreeRef for plain node-addressed trees (column c -> slab c)
 TreeRef slab_tree_ref(uint8_t *d_tree, size_t npad);
 // copies node `node` of every column's tree into d_out[c][32]
@@ -503,6 +514,23 @@ void launch_mbatch_level(const MBatchTab *d_tabs, unsigned nt, unsigned nwg, hip
 void launch_mbatch_roots(const MBatchTab *d_tabs, unsigned nt, uint8_t *h_roots, hipStream_t s, DoneFlag done);
 void launch_mbatch_eval(const MEvalTab *d_tabs, unsigned nt, unsigned nwg, hipStream_t s);
 void launch_mbatch_paths(const MPathTab *d_tabs, unsigned nt, const MPathOut &out, hipStream_t s, DoneFlag done);
+// Many openings of a batch's trees in one launch (zigz_merkle_open_many): the work item is 16 bytes of one sibling digest, the
+// lanes follow the OUTPUT (consecutive lanes store consecutive 16 bytes of the packed siblings) and gather from the trees.
+struct MOpenTree {  // one tree of the batch
+    const uint8_t *tree;
+    const uint32_t *vals;
+    uint64_t npad;
+    uint32_t height, reserved;
+};
+struct MOpenOut {  // where a chunk's openings go (pinned host memory, or the caller's device arrays): siblings / directions at
+    uint8_t *sib, *dirs;  // the opening's slot within the chunk, leaf values and roots (may be null) at its position
+    uint64_t *leaf;
+    uint8_t *roots;
+};
+// k openings with `slots` sibling slots (descriptor j's off: its first slot); zero_height: some opening has no siblings and
+// is served by a one-thread-per-opening pass in the same launch; nt: non-temporal stores (device outputs)
+void launch_mbatch_open_many(const MOpenTree *d_trees, const mo::Desc *d_desc, unsigned k, unsigned slots, bool zero_height,
+                             const MOpenOut &out, bool nt, hipStream_t s, DoneFlag done);
 
 // ---- batched Merkle verification (merkle_verify.hip): SimpleMerkleTree.verify for k independent openings, one lane per
 // opening.  The openings are sorted by height (a stable counting sort on the host); a bucket is a run of sorted positions of

@@ -173,6 +173,65 @@ __global__ __launch_bounds__(64) void k_mbatch_paths(const MPathTab *__restrict_
     signal_done_block(done, gridDim.x);
 }
 
+// Many openings of the batch's trees (zigz_merkle_open_many): any number per tree, in the caller's order.  The work item is 16
+// bytes of one sibling digest: a workgroup owns TPB / 2 consecutive sibling slots of the packed output, consecutive lanes store
+// consecutive 16 bytes, and the reads from the trees are the scattered side.  The workgroup finds the openings of its first and
+// last slot by a binary search over the descriptors' slot offsets (uniform: scalar loads), a lane its own opening between the
+// two.  Openings of height 0 share their offset with the opening after them: the LAST descriptor whose offset is <= the slot
+// owns it.  The lanes of an opening's level 0 also write its leaf value and root; an opening without siblings has no such
+// lane, so the workgroups behind the sibling workgroups take one opening per thread and serve those.
+__device__ __forceinline__ unsigned mo_find(const mo::Desc *__restrict__ desc, unsigned lo, unsigned hi, unsigned slot) {
+    while (hi - lo > 1) {
+        const unsigned mid = (lo + hi) >> 1;
+        if (desc[mid].off <= slot) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+template <bool NT>
+__device__ __forceinline__ void mo_store16(uint8_t *p, const uint4 &v) {
+    if (NT) nt_store16(reinterpret_cast<uint4 *>(p), v);
+    else *reinterpret_cast<uint4 *>(p) = v;
+}
+template <bool NT>
+__global__ __launch_bounds__(TPB) void k_mbatch_open_many(const MOpenTree *__restrict__ trees, const mo::Desc *__restrict__ desc,
+                                                          unsigned k, unsigned slots, unsigned sib_wgs, MOpenOut out, DoneFlag done) {
+    if (blockIdx.x < sib_wgs) {
+        const unsigned s0 = blockIdx.x * (TPB / 2);
+        const unsigned s1 = (slots - s0 < TPB / 2 ? slots : s0 + TPB / 2) - 1;
+        const unsigned j0 = mo_find(desc, 0, k, s0), j1 = mo_find(desc, j0, k, s1);
+        const unsigned slot = s0 + (threadIdx.x >> 1), half = threadIdx.x & 1;
+        if (slot <= s1) {
+            const unsigned j = mo_find(desc, j0, j1 + 1, slot);
+            const mo::Desc d = desc[j];
+            const MOpenTree T = trees[d.tree];
+            const unsigned l = slot - d.off;
+            const uint64_t ci = d.index >> l;  // current_index at level l; its sibling is node ci ^ 1
+            const uint4 v = canonical_half(T.tree + (slab_level_offset(T.npad, l) + (ci ^ 1)) * 32 + half * 16);
+            mo_store16<NT>(out.sib + (size_t)slot * 32 + half * 16, v);
+            if (!half) out.dirs[slot] = (uint8_t)(ci & 1);  // directions[l] = is_right
+            if (l == 0) {
+                if (!half) out.leaf[j] = T.vals[d.index];
+                if (out.roots) mo_store16<NT>(out.roots + (size_t)j * 32 + half * 16, canonical_half(T.tree + (2 * T.npad - 2) * 32 + half * 16));
+            }
+        }
+    } else {
+        const unsigned j = (blockIdx.x - sib_wgs) * TPB + threadIdx.x;
+        if (j < k) {
+            const mo::Desc d = desc[j];
+            const MOpenTree T = trees[d.tree];
+            if (T.height == 0) {  // one leaf: it is the root
+                out.leaf[j] = T.vals[d.index];
+                if (out.roots) {
+                    mo_store16<NT>(out.roots + (size_t)j * 32, canonical_half(T.tree));
+                    mo_store16<NT>(out.roots + (size_t)j * 32 + 16, canonical_half(T.tree + 16));
+                }
+            }
+        }
+    }
+    signal_done_block(done, gridDim.x);
+}
+
 void launch_mbatch_subtrees(const MBatchTab *d_tabs, unsigned nt, unsigned nwg, hipStream_t s) {
     hipLaunchKernelGGL(k_mbatch_subtrees, dim3(nwg), dim3(TPB), 0, s, d_tabs, nt);
 }
@@ -187,6 +246,13 @@ void launch_mbatch_eval(const MEvalTab *d_tabs, unsigned nt, unsigned nwg, hipSt
 }
 void launch_mbatch_paths(const MPathTab *d_tabs, unsigned nt, const MPathOut &out, hipStream_t s, DoneFlag done) {
     hipLaunchKernelGGL(k_mbatch_paths, dim3(nt), dim3(64), 0, s, d_tabs, nt, out, done);
+}
+
+void launch_mbatch_open_many(const MOpenTree *d_trees, const mo::Desc *d_desc, unsigned k, unsigned slots, bool zero_height,
+                             const MOpenOut &out, bool nt, hipStream_t s, DoneFlag done) {
+    const unsigned sib_wgs = (slots + TPB / 2 - 1) / (TPB / 2), grid = sib_wgs + (zero_height ? (k + TPB - 1) / TPB : 0);
+    if (nt) hipLaunchKernelGGL(k_mbatch_open_many<true>, dim3(grid), dim3(TPB), 0, s, d_trees, d_desc, k, slots, sib_wgs, out, done);
+    else hipLaunchKernelGGL(k_mbatch_open_many<false>, dim3(grid), dim3(TPB), 0, s, d_trees, d_desc, k, slots, sib_wgs, out, done);
 }
 
 }  // namespace zk

@@ -50,6 +50,20 @@ __device__ __forceinline__ Digest load_digest(const uint8_t *tree, size_t node) 
     return Digest{{x.x, x.y, y.x, y.y}};
 }
 
+// One 64-bit word of a digest, tree form -> SHA3 bytes (canonical_digest works word by word: a digest can be split over lanes)
+__device__ __forceinline__ uint64_t canonical_word(uint64_t t) {
+    const uint32_t e = (uint32_t)t, o = (uint32_t)(t >> 32);
+    const uint32_t lo = expand_even(e) | (expand_even(o) << 1);
+    const uint32_t hi = expand_even(e >> 16) | (expand_even(o >> 16) << 1);
+    return ((uint64_t)hi << 32) | lo;
+}
+// 16 bytes of a digest in tree form at p -> the same 16 bytes of its canonical form
+__device__ __forceinline__ uint4 canonical_half(const uint8_t *p) {
+    const ulonglong2 x = *reinterpret_cast<const ulonglong2 *>(p);
+    const uint64_t a = canonical_word(x.x), b = canonical_word(x.y);
+    return make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
+}
+
 __device__ __forceinline__ void store_digest_plain(uint8_t *tree, size_t node, const Digest &d) {
     unsigned long long *q = reinterpret_cast<unsigned long long *>(tree + node * 32);
     q[0] = d.w[0]; q[1] = d.w[1]; q[2] = d.w[2]; q[3] = d.w[3];

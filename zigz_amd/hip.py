@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import errors
-from ._ffi import BenchResult, KernelStats, lib, u8p, u64p, vp
+from ._ffi import BenchResult, KernelStats, lib, u8p, u32p, u64p, vp
 
 P = 2013265921
 NUM_COLUMNS = 43
@@ -656,6 +656,43 @@ class MerkleBatch:
             o += v
         return out
 
+    def _many_args(self, trees, indices):
+        t = np.ascontiguousarray(np.asarray(trees, dtype=np.uint32).reshape(-1))
+        ix = np.ascontiguousarray(np.asarray(indices, dtype=np.uint64).reshape(-1))
+        if len(t) != len(ix):
+            raise ValueError(f"{len(t)} trees for {len(ix)} indices")
+        hs = np.asarray(self.heights + [0], dtype=np.int64)[np.minimum(t, len(self.heights))]  # (a bad tree id: the call rejects it)
+        pad = (lambda a: a if a.size else np.zeros(1, a.dtype))
+        return pad(t), pad(ix), len(t), int(hs.sum())
+
+    def open_many(self, trees, indices):
+        """zigz_merkle_open_many: tree_{trees[j]}.open(indices[j]) for every j, any number per tree.  Returns a dict of numpy
+        arrays in the shapes Context.merkle_verify_batch takes: roots (k x 32), heights (k), leaves (k), and siblings (32 B
+        each) and dirs packed opening by opening."""
+        t, ix, k, tot = self._many_args(trees, indices)
+        sib, sp = _out_u8(32 * tot)
+        dirs, dp = _out_u8(tot)
+        leaf, lp = _out_u64(k)
+        roots, rp = _out_u8(32 * k)
+        hs = (C.c_size_t * max(k, 1))()
+        bad = C.c_size_t(0)
+        self.ctx.check_batch(lib.zigz_merkle_open_many(self.ctx.h, self.h, k, t.ctypes.data_as(u32p), ix.ctypes.data_as(u64p), sp, dp,
+                                                       lp, rp, hs, C.byref(bad)), bad)
+        return dict(roots=roots[: 32 * k].reshape(k, 32), heights=np.array(hs[:k], dtype=np.int64), leaves=leaf[:k],
+                    siblings=sib[: 32 * tot], dirs=dirs[:tot])
+
+    def dev_open_many(self, trees, indices, d_siblings, d_dirs, d_leaves, d_roots=None):
+        """zigz_dev_merkle_open_many: the same into device memory (addresses; d_siblings and d_roots 16-byte aligned, d_leaves
+        8-byte aligned) in the layout Context.dev_merkle_verify_batch takes; queued on the context's stream.  Returns the
+        heights (host)."""
+        t, ix, k, _ = self._many_args(trees, indices)
+        hs = (C.c_size_t * max(k, 1))()
+        bad = C.c_size_t(0)
+        self.ctx.check_batch(lib.zigz_dev_merkle_open_many(self.ctx.h, self.h, k, t.ctypes.data_as(u32p), ix.ctypes.data_as(u64p),
+                                                           vp(d_siblings), vp(d_dirs), vp(d_leaves), vp(d_roots) if d_roots else None,
+                                                           hs, C.byref(bad)), bad)
+        return np.array(hs[:k], dtype=np.int64)
+
     def deinit(self):
         if self.h:
             lib.zigz_merkle_batch_destroy(self.ctx.h, self.h)
@@ -727,6 +764,26 @@ class CommitJob:
         self.ctx.check(lib.zigz_commit_open_all(self.j, pp, vpp, ip, lp, sp, dp))
         return dict(values=values[:nc], indices=idx[:nc], leaves=leaves[:nc],
                     siblings=sib[: nc * nv * 32].reshape(nc, nv, 32), dirs=dirs[: nc * nv].reshape(nc, nv))
+
+    def open_many(self, cols, indices):
+        """zigz_commit_open_many: k openings of the job's trees (cols[j] in the job's column numbering, indices[j] < 2^nv),
+        valid after roots().  Returns dict(leaves (k), siblings (k x nv x 32), dirs (k x nv))."""
+        if not self.j:  # ended: the handle is gone
+            raise errors.ZigzError(errors.BAD_STATE, _name(errors.BAD_STATE), "the commit job has ended")
+        c = np.ascontiguousarray(np.asarray(cols, dtype=np.uint32).reshape(-1))
+        ix = np.ascontiguousarray(np.asarray(indices, dtype=np.uint64).reshape(-1))
+        if len(c) != len(ix):
+            raise ValueError(f"{len(c)} columns for {len(ix)} indices")
+        k, nv = len(c), self.nv
+        if k == 0:
+            c, ix = np.zeros(1, np.uint32), np.zeros(1, np.uint64)
+        sib, sp = _out_u8(k * nv * 32)
+        dirs, dp = _out_u8(k * nv)
+        leaf, lp = _out_u64(k)
+        bad = C.c_size_t(0)
+        self.ctx.check_batch(lib.zigz_commit_open_many(self.j, k, c.ctypes.data_as(u32p), ix.ctypes.data_as(u64p), sp, dp, lp,
+                                                       C.byref(bad)), bad)
+        return dict(leaves=leaf[:k], siblings=sib[: k * nv * 32].reshape(k, nv, 32), dirs=dirs[: k * nv].reshape(k, nv))
 
     def tree(self):
         """(device address, bytes per column) of the built trees, internal node form -- for node-by-node comparisons."""
