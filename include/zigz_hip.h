@@ -542,6 +542,55 @@ zigz_status zigz_dev_merkle_verify_batch(zigz_ctx *ctx, size_t k, const uint8_t 
                                          const uint64_t *d_leaf_values, const uint8_t *d_siblings, const uint8_t *d_dirs,
                                          uint8_t *verdicts, size_t *n_rejected, size_t *bad_index);
 
+/* k independent Multilinear.eval calls (multilinear.zig:110-144; point[0] <-> LSB of the index) in shared launches: one launch
+ * evaluates every (table, point) pair, a second hands the k results over.  Pair i: table i of ns[i] = 2^v_i elements and the v_i
+ * coordinates at points + sum_{j<i} v_j (concatenated in pair order, like zigz_dev_sumcheck_prove_batch's points); out[i] is
+ * byte-identical to zigz_dev_mle_eval(d_tables[i], ns[i], point_i, v_i) -- for ns[i] = 1 the table's one value.  The same
+ * table may appear any number of times, with the same or different points.  k <= ZIGZ_BATCH_MAX, else
+ * ZIGZ_ERR_INVALID_ARGUMENT; k == 0 returns ZIGZ_OK and touches nothing.  d_tables[i] must be 16-byte aligned, ns[i] <= 2^32 and
+ * the call's tables together fewer than 2^24 chunks of 8192 elements, one launch's grid (ZIGZ_ERR_INVALID_ARGUMENT otherwise).  Every argument is checked for every pair before anything is launched or written: on
+ * the first pair (in index order) that the single entry would reject, or whose point holds a coordinate >= p
+ * (ZIGZ_ERR_NOT_CANONICAL), the call returns that status and writes the pair's index to *bad_index (if non-NULL).  Leaves the
+ * hint options, zigz_kernel_stats, an active commit job and open zigz_merkle_batch handles alone; queues on the context's stream. */
+zigz_status zigz_dev_mle_eval_batch(zigz_ctx *ctx, const uint32_t *const *d_tables, const size_t *ns, size_t k,
+                                    const uint64_t *points, uint64_t *out, size_t *bad_index);
+/* host tables (canonical u64, ZIGZ_ERR_NOT_CANONICAL with the pair's index otherwise), narrowed and uploaded in one copy;
+ * zigz_mle_eval is the single entry */
+zigz_status zigz_mle_eval_batch(zigz_ctx *ctx, const uint64_t *const *tables, const size_t *ns, size_t k,
+                                const uint64_t *points, uint64_t *out, size_t *bad_index);
+/* k independent SumcheckVerifier.verify calls (src/proofs/sumcheck_verifier.zig:48-108) whose oracle is the multilinear
+ * extension of table i: the k oracle evaluations run in the batched eval's launch while the host replays the k transcripts.
+ * Proof i, in the layout zigz_dev_sumcheck_prove_batch writes: ns[i] = 2^v_i, rounds (2 v_i words [c0, c1] per round) and
+ * points (v_i words) concatenated in proof order, claimed_sums[i], final_evals[i].  Per proof, bit for bit the reference: a
+ * fresh transcript, claim = claimed_sums[i]; per round reject if g(0) + g(1) != claim, absorb c0 and c1, draw the challenge
+ * (sumcheck_protocol.zig:176-184), claim = g(challenge); then oracle_eval = eval(table_i, point_i) and the proof is accepted iff
+ * oracle_eval == claim && oracle_eval == final_evals[i].
+ * Outputs: verdicts[i] (may be NULL) 1 accept / 0 reject; *n_rejected the number of rejects; expected_evals[i] (may be NULL)
+ * VerificationResult.expected_eval -- the claim at the failing round, or the final claim; oracle_evals[i] (may be NULL) the
+ * evaluation, written for every proof including those whose rounds failed.
+ * POINT ORDER.  flags == 0 evaluates the oracle at the proof's final point as given, point[0] <-> LSB, exactly as the reference's
+ * verifier does.  The prover binds MSB-first, so with the proved table as the oracle an honest proof of two or more variables is
+ * REJECTED in general -- that is the reference's behaviour and the default reproduces it.  ZIGZ_SUMCHECK_VERIFY_POINT_REVERSED
+ * evaluates at the reversed point, where the prover's final_eval lives: honest proofs are accepted.  (One variable: both agree.)
+ * Statuses are for the shape of the arguments only, never for what a proof holds: ZIGZ_ERR_INVALID_ARGUMENT for ctx or
+ * n_rejected NULL, an unknown flag, a NULL input array when k > 0, k > ZIGZ_BATCH_MAX, a table that is NULL, not 16-byte aligned
+ * or larger than 2^32; the prover's rules per table (zigz_dev_sumcheck_prove: ns[i] = 1 is ZIGZ_ERR_NO_VARIABLES);
+ * ZIGZ_ERR_NOT_CANONICAL for a point coordinate, round coefficient, claimed sum or final eval >= p.  All checked for every proof
+ * before anything is launched or written; the first failing proof's index goes to *bad_index (if non-NULL).  k == 0: ZIGZ_OK,
+ * *n_rejected = 0, nothing else touched.  Leaves alone what zigz_dev_mle_eval_batch leaves alone. */
+#define ZIGZ_SUMCHECK_VERIFY_POINT_REVERSED 1u
+zigz_status zigz_dev_sumcheck_verify_batch(zigz_ctx *ctx, const uint32_t *const *d_tables, const size_t *ns, size_t k,
+                                           const uint64_t *claimed_sums, const uint64_t *rounds, const uint64_t *points,
+                                           const uint64_t *final_evals, uint32_t flags, uint8_t *verdicts,
+                                           uint64_t *expected_evals, uint64_t *oracle_evals, size_t *n_rejected,
+                                           size_t *bad_index);
+/* host tables (canonical u64, ZIGZ_ERR_NOT_CANONICAL with the proof's index otherwise), narrowed and uploaded in one copy */
+zigz_status zigz_sumcheck_verify_batch(zigz_ctx *ctx, const uint64_t *const *tables, const size_t *ns, size_t k,
+                                       const uint64_t *claimed_sums, const uint64_t *rounds, const uint64_t *points,
+                                       const uint64_t *final_evals, uint32_t flags, uint8_t *verdicts,
+                                       uint64_t *expected_evals, uint64_t *oracle_evals, size_t *n_rejected,
+                                       size_t *bad_index);
+
 /* ---------------------------------------------------------------- host SHA3 sponge / transcript
  * FiatShamirTranscript   src/core/hash.zig:255-324 (sequential by construction: stays on the host) */
 zigz_transcript *zigz_transcript_new(void);

@@ -144,7 +144,7 @@ def generate():
     w("//! bodies of the replaced reference functions: INTEGRATION.md.")
     w("")
     w("pub const Status = i32;")
-    for name, val in re.findall(r"#define (ZIGZ_[A-Z_0-9]+) (\d+)(?:ull)?\b", raw):
+    for name, val in re.findall(r"#define (ZIGZ_[A-Z_0-9]+) (\d+)(?:ull|u)?\b", raw):
         w("pub const %s = %s;" % (name.replace("ZIGZ_", ""), val))
     w("")
     w("// zigz_status values (the Zig error each one maps back to is in the header comment of the code)")

@@ -154,6 +154,12 @@ SIGNATURES = {
     "zigz_merkle_batch_destroy": (None, [vp, vp]),
     "zigz_merkle_verify_batch": (C.c_int32, [vp, C.c_size_t, u8p, szp, u64p, u8p, u8p, u8p, szp, szp]),
     "zigz_dev_merkle_verify_batch": (C.c_int32, [vp, C.c_size_t, vp, szp, vp, vp, vp, u8p, szp, szp]),
+    "zigz_dev_mle_eval_batch": (C.c_int32, [vp, C.POINTER(vp), szp, C.c_size_t, u64p, u64p, szp]),
+    "zigz_mle_eval_batch": (C.c_int32, [vp, C.POINTER(u64p), szp, C.c_size_t, u64p, u64p, szp]),
+    "zigz_dev_sumcheck_verify_batch": (C.c_int32, [vp, C.POINTER(vp), szp, C.c_size_t, u64p, u64p, u64p, u64p, C.c_uint32, u8p, u64p,
+                                                   u64p, szp, szp]),
+    "zigz_sumcheck_verify_batch": (C.c_int32, [vp, C.POINTER(u64p), szp, C.c_size_t, u64p, u64p, u64p, u64p, C.c_uint32, u8p, u64p,
+                                               u64p, szp, szp]),
     "zigz_sumcheck_radix_run_batch": (C.c_int32, [vp, RB_BLOCK_SUMS_FN, RB_FOLD_FN, RB_READ_TAIL_FN, C.c_size_t, szp, u64p, u64p, u64p,
                                                   u64p]),
     "zigz_dev_sumcheck_prove_rccl": (C.c_int32, [vp, vp, C.c_size_t, vp, u64p, u64p, u64p]),

@@ -19,12 +19,13 @@
 
 #include "field.hpp"
 #include "host_hash.hpp"
+#include "host_parallel.hpp"
 #include "kernels.hpp"
 
 using namespace zk;
 
 // ------------------------------------------------------------------ context
-enum { WS_IN64 = 0, WS_IN32, WS_OUT32, WS_OUT64, WS_SCRATCH, WS_TREE, WS_FOLD, WS_MISC, WS_COLS, WS_LASSO, WS_DEDUP, WS_WITNESS, WS_RUNS, WS_RUNMETA, WS_CONS, WS_CONSMETA, WS_BATCH, WS_SCBATCH, WS_SCBATCH_IN, WS_VERIFY, WS_OPEN, WS_SLOTS };
+enum { WS_IN64 = 0, WS_IN32, WS_OUT32, WS_OUT64, WS_SCRATCH, WS_TREE, WS_FOLD, WS_MISC, WS_COLS, WS_LASSO, WS_DEDUP, WS_WITNESS, WS_RUNS, WS_RUNMETA, WS_CONS, WS_CONSMETA, WS_BATCH, WS_SCBATCH, WS_SCBATCH_IN, WS_VERIFY, WS_OPEN, WS_MLEBATCH, WS_MLEBATCH_PART, WS_MLEBATCH_IN, WS_SLOTS };
 
 constexpr int KEV_MAX = 72;
 struct ListCaps {

@@ -555,4 +555,25 @@ struct MVerifyArgs {
 // dev: the device form's gather; pause: sha3 with the re-arm pauses (keccak.hpp)
 void launch_mverify(const MVerifyTab *d_tabs, unsigned nt, unsigned nwg, const MVerifyArgs &a, bool dev, bool pause, hipStream_t s);
 
+// ---- batched MLE evaluation over free-standing tables (mle_batch.hip): eval(point) of k (table, point) pairs in one launch.
+// A workgroup owns one chunk of MLE_BATCH_CHUNK consecutive elements of one table (a smaller table is one partial chunk).
+constexpr unsigned MLE_BATCH_CHUNK = 8192;
+constexpr size_t MLE_BATCH_MAX_WGS = ((size_t)1 << 24) - 1;  // workgroups of 256 threads per launch: a grid holds fewer than 2^32 threads
+constexpr unsigned MLE_BATCH_MAX_LOG2_N = 32;  // largest table: the exact u64 sum of a pair cannot wrap (mle_batch.hip)
+struct MleBatchTab {  // one pair; its workgroups are [first_wg, first_wg of pair j + 1)
+    const uint32_t *vals;  // 2^nv packed canonical values, 16-byte aligned
+    uint64_t n;
+    uint32_t nv;
+    uint32_t first_wg;
+    uint32_t f_off;  // the pair's 2 nv factors in the factor array, Montgomery form: [2 v] = 1 - r_v, [2 v + 1] = r_v, where r_v
+                     // is the coordinate bound to index bit v
+    uint32_t slot;   // the pair's result slot
+};
+// part: one exact u64 partial sum per workgroup of the launch (nwg words, all written)
+void launch_mle_batch_eval(const MleBatchTab *d_tabs, unsigned nt, unsigned nwg, const uint32_t *d_f, unsigned long long *d_part,
+                           hipStream_t s);
+// one workgroup per pair: its partials added, reduced mod p once, into pinned h_out[slot] (u64); completion signalled under `done`
+void launch_mle_batch_finish(const MleBatchTab *d_tabs, unsigned nt, const unsigned long long *d_part, uint64_t *h_out, hipStream_t s,
+                             DoneFlag done);
+
 }  // namespace zk

@@ -1,0 +1,165 @@
+// Batched MLE evaluation over free-standing tables: k independent Multilinear.eval calls (multilinear.zig:110-144) in ONE launch.
+//
+// eval(point) = sum_i T[i] * prod_v f_v[bit v of i], f_v = (1 - r_v, r_v), r_v the coordinate bound to index bit v.  The launch
+// reads a table of per-pair descriptors (MleBatchTab, kernels.hpp); every workgroup finds its pair by a binary search over the
+// prefix of workgroup counts, as the batched sumcheck and the batched Merkle builds do, and owns one chunk of MLE_BATCH_CHUNK
+// (8192) consecutive elements of that pair's table: 8 streaming 16-byte loads per lane, issued back to back.
+//
+// The weight of element i factors along its index bits, and the chunk layout i = base + 4 (256 j + thread) + c splits them into
+//   bits  0-1  c       and bits 10-12  j : 32 workgroup-uniform weights U[j][c], built once per workgroup in LDS
+//   bits  2-9  thread                    : two 16-entry tables A (bits 2-5), B (bits 6-9) in LDS, one product per lane
+//   bits 13+   workgroup                 : one uniform factor H (a product over the lanes of one wave)
+// so a lane forms  sum_{j,c} U[j][c] * T[..]  with ONE widening multiply per element and no reduction inside the loop (32-bit
+// multiplies issue at under half rate on gfx950; see k_radix_fold): U is in Montgomery form (u R), the 64-bit products are added
+// as separate low and high halves, and  hi + monty_reduce(lo)  is congruent to  sum u T  (k_radix_fold's deferred reduction).
+// One Montgomery reduction and one multiply by the lane's weight A B H turn that into the lane's term.  A variable past the
+// table's own (a table smaller than a chunk) has the factor pair (1, 0): every element that does not exist gets weight 0 and
+// its load is clamped to the chunk's first 16 bytes.
+//
+// Exact arithmetic: every lane term is a canonical product below p; a pair's terms -- at most one per 32 elements, at least
+// one -- are added in u64: a shuffle sum per wave, the four waves through LDS, and ONE plain store per workgroup into a
+// partial array indexed by the workgroup's number (no atomics: with one accumulator per pair the 512 .. 2048 waves of a
+// 2^20 .. 2^22 table queued up behind one cache line, and the launch ran at a tenth of the HBM rate).  k_mle_batch_finish, one
+// workgroup per pair, adds the pair's partials, reduces mod p ONCE and writes the result into pinned memory, then signals the
+// host (signal_done_block: fence, barrier, then count).  With n <= 2^MLE_BATCH_MAX_LOG2_N a pair's sum stays below
+// 2^31 * n <= 2^63 and cannot wrap.  Every partial is written by every launch, so nothing has to be zeroed between calls.
+#include "kernels.hpp"
+
+#include "field.hpp"
+#include "tree_dev.hpp"
+
+namespace zk {
+
+namespace {
+
+constexpr int ME_LOADS = MLE_BATCH_CHUNK / (4 * TPB);  // 16-byte loads per lane
+constexpr unsigned ME_LANE_BIT = 2, ME_LOOP_BIT = 10, ME_HI_BIT = 13;  // first index bit of the thread, the load, the workgroup
+static_assert(ME_LOADS == 8 && MLE_BATCH_CHUNK == 1u << ME_HI_BIT, "index bits: 2 component, 8 thread, 3 load, the rest workgroup");
+static_assert(TPB == 256, "A and B cover the thread's 8 index bits, wave 1 the high variables, four wave sums per workgroup");
+static_assert(31 + MLE_BATCH_MAX_LOG2_N < 64, "a pair's exact u64 sum: fewer than n terms below p < 2^31");
+static_assert(ME_HI_BIT + 64 > MLE_BATCH_MAX_LOG2_N, "one wave holds a factor per high variable");
+
+__device__ __forceinline__ uint4 me_stream_load(const uint4 *q) {
+    const zk_v4u v = __builtin_nontemporal_load(reinterpret_cast<const zk_v4u *>(q));
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+// the pair that owns workgroup `wg`: the last one whose first workgroup is <= wg
+__device__ __forceinline__ unsigned me_find(const MleBatchTab *__restrict__ tabs, unsigned nt, unsigned wg) {
+    unsigned lo = 0, hi = nt;
+    while (hi - lo > 1) {
+        const unsigned mid = (lo + hi) >> 1;
+        if (tabs[mid].first_wg <= wg) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// prod_{i < cnt} f_{v0 + i}[bit i of bits], Montgomery form; a variable the table does not have contributes (1, 0)
+__device__ __forceinline__ uint32_t me_eq(const uint32_t *__restrict__ f, unsigned nv, unsigned v0, unsigned cnt, unsigned bits) {
+    uint32_t w = R_MOD_P;
+    for (unsigned i = 0; i < cnt; i++) {
+        const unsigned v = v0 + i, b = (bits >> i) & 1;
+        w = mont_mul(w, v < nv ? f[2 * v + b] : (b ? 0u : R_MOD_P));
+    }
+    return w;
+}
+
+__device__ __forceinline__ unsigned long long me_wave_sum(unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(TPB) void k_mle_batch_eval(const MleBatchTab *__restrict__ tabs, unsigned nt,
+                                                        const uint32_t *__restrict__ factors, unsigned long long *__restrict__ part) {
+    ZK_PRIO_SMALL();
+    __shared__ __align__(16) uint32_t s_u[4 * ME_LOADS];
+    __shared__ uint32_t s_a[16], s_b[16], s_hi;
+    __shared__ unsigned long long s_sum[TPB / 64];
+    const MleBatchTab d = tabs[me_find(tabs, nt, blockIdx.x)];
+    const uint32_t *f = factors + d.f_off;
+    const unsigned t = threadIdx.x, nv = d.nv;
+    const size_t base = (size_t)(blockIdx.x - d.first_wg) * MLE_BATCH_CHUNK;
+    if (t < 32) {
+        s_u[t] = mont_mul(me_eq(f, nv, 0, ME_LANE_BIT, t & 3), me_eq(f, nv, ME_LOOP_BIT, ME_HI_BIT - ME_LOOP_BIT, t >> 2));
+    } else if (t < 48) {
+        s_a[t - 32] = me_eq(f, nv, ME_LANE_BIT, 4, t - 32);
+    } else if (t < 64) {
+        s_b[t - 48] = me_eq(f, nv, ME_LANE_BIT + 4, 4, t - 48);
+    } else if (t < 128) {  // wave 1: H, the factors of the workgroup's own index bits multiplied across the lanes
+        const unsigned v = ME_HI_BIT + (t - 64);
+        uint32_t w = v < nv ? f[2 * v + (unsigned)((base >> v) & 1)] : R_MOD_P;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) w = mont_mul(w, __shfl_down(w, off, 64));
+        // one more factor R: the lane's sum arrives divided by R (monty_reduce below)
+        if (t == 64) s_hi = mont_mul(w, R2_MOD_P);
+    }
+    __syncthreads();
+    unsigned long long lo = 0, hi = 0;
+    if (d.n >= 4) {  // uniform over the workgroup
+        const uint4 *p = reinterpret_cast<const uint4 *>(d.vals);
+        const size_t nq = d.n / 4, q0 = base / 4;
+        uint4 v[ME_LOADS];
+#pragma unroll
+        for (int j = 0; j < ME_LOADS; j++) {
+            const size_t q = q0 + (size_t)j * TPB + t;
+            v[j] = me_stream_load(p + (q < nq ? q : q0));  // clamped, not branched: the loads are issued back to back
+        }
+#pragma unroll
+        for (int j = 0; j < ME_LOADS; j++) {
+            const uint4 u = reinterpret_cast<const uint4 *>(s_u)[j];  // uniform address: one LDS read per wave
+            const uint32_t uu[4] = {u.x, u.y, u.z, u.w}, e[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                const unsigned long long pr = (unsigned long long)uu[c] * e[c];
+                lo += (uint32_t)pr;
+                hi += pr >> 32;
+            }
+        }
+    } else if (t == 0) {  // one or two elements: no 16 bytes to load
+        for (unsigned c = 0; c < (unsigned)d.n; c++) {
+            const unsigned long long pr = (unsigned long long)s_u[c] * d.vals[c];
+            lo += (uint32_t)pr;
+            hi += pr >> 32;
+        }
+    }
+    // lo < 32 * 2^32 and hi < 32 * 2^31: hi + monty_reduce(lo) < 2^37 is congruent to sum u T; reduced once more it is that sum / R
+    const uint32_t s = monty_reduce(hi + monty_reduce(lo));
+    const uint32_t w = mont_mul(mont_mul(s_a[t & 15], s_b[t >> 4]), s_hi);  // A B H R^2
+    unsigned long long term = mont_mul(w, s);                               // canonical, < p
+    term = me_wave_sum(term);
+    if ((t & 63) == 0) s_sum[t >> 6] = term;
+    __syncthreads();
+    if (t == 0) part[blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+}
+
+// One workgroup per pair: the pair's partial sums (one per workgroup of the eval launch, consecutive) added up, reduced mod p
+// once and written into pinned memory at the pair's result slot.
+__global__ __launch_bounds__(TPB) void k_mle_batch_finish(const MleBatchTab *__restrict__ tabs, const unsigned long long *__restrict__ part,
+                                                          uint64_t *h_out, DoneFlag done) {
+    __shared__ unsigned long long s_sum[TPB / 64];
+    const MleBatchTab d = tabs[blockIdx.x];
+    const size_t cnt = (size_t)((d.n + MLE_BATCH_CHUNK - 1) / MLE_BATCH_CHUNK);
+    const unsigned long long *p = part + d.first_wg;
+    unsigned long long sum = 0;
+    for (size_t j = threadIdx.x; j < cnt; j += TPB) sum += p[j];
+    sum = me_wave_sum(sum);
+    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) h_out[d.slot] = (s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]) % (unsigned long long)P;
+    signal_done_block(done, gridDim.x);  // (TPB threads: several waves; no thread returns early)
+}
+
+void launch_mle_batch_eval(const MleBatchTab *d_tabs, unsigned nt, unsigned nwg, const uint32_t *d_f, unsigned long long *d_part,
+                           hipStream_t s) {
+    hipLaunchKernelGGL(k_mle_batch_eval, dim3(nwg), dim3(TPB), 0, s, d_tabs, nt, d_f, d_part);
+}
+void launch_mle_batch_finish(const MleBatchTab *d_tabs, unsigned nt, const unsigned long long *d_part, uint64_t *h_out, hipStream_t s,
+                             DoneFlag done) {
+    hipLaunchKernelGGL(k_mle_batch_finish, dim3(nt), dim3(TPB), 0, s, d_tabs, d_part, h_out, done);
+}
+
+}  // namespace zk

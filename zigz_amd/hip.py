@@ -24,6 +24,7 @@ TRACE_STEP32_DTYPE = np.dtype([("pc", "<u8"), ("rd_value", "<u8"), ("imm", "<i4"
 MEM_ACCESS_DTYPE = np.dtype([("addr", "<u8"), ("value", "<u8")])
 assert TRACE_STEP32_DTYPE.itemsize == 32 and MEM_ACCESS_DTYPE.itemsize == 16
 NO_MEM_ACCESS = 0xFFFFFFFF
+SUMCHECK_VERIFY_POINT_REVERSED = 1  # ZIGZ_SUMCHECK_VERIFY_POINT_REVERSED: the oracle at the reversed point (honest proofs accept)
 
 
 def compact_steps32(steps, has_access):
@@ -409,6 +410,64 @@ class Context:
         bad = C.c_size_t(0)
         self.check_batch(lib.zigz_dev_sumcheck_prove_batch(self.h, ptrs, nsa, k, cp, rp, ptp, fep, C.byref(bad)), bad)
         return self._batch_split(nvs, r, pt, fe)
+
+    # ---- batched MLE evaluation and sumcheck verification (k independent pairs / proofs per call, one eval launch)
+    @staticmethod
+    def _cat_u64(parts):
+        return _u64(np.concatenate([np.asarray(x, dtype=np.uint64).reshape(-1) for x in parts] + [np.zeros(1, np.uint64)]))
+
+    def mle_eval_batch(self, tables, points):
+        """zigz_mle_eval_batch: mle_eval(tables[i], points[i]) for every pair, in shared launches.  Returns the k values."""
+        k = len(tables)
+        arrs = [_u64(t) for t in tables]
+        ns = (C.c_size_t * max(k, 1))(*[len(t) for t in tables])
+        ptrs = (u64p * max(k, 1))(*[p for _, p in arrs])
+        q, qp = self._cat_u64(points)
+        o, op = _out_u64(k)
+        bad = C.c_size_t(0)
+        self.check_batch(lib.zigz_mle_eval_batch(self.h, ptrs, ns, k, qp, op, C.byref(bad)), bad)
+        return [int(x) for x in o[:k]]
+
+    def dev_mle_eval_batch(self, d_tables, ns, points):
+        """zigz_dev_mle_eval_batch over device-resident tables (packed u32 canonical, 16-byte aligned); points[i] has
+        log2(ns[i]) coordinates."""
+        k = len(ns)
+        nsa = (C.c_size_t * max(k, 1))(*[int(n) for n in ns])
+        ptrs = (vp * max(k, 1))(*[int(d) for d in d_tables])
+        q, qp = self._cat_u64(points)
+        o, op = _out_u64(k)
+        bad = C.c_size_t(0)
+        self.check_batch(lib.zigz_dev_mle_eval_batch(self.h, ptrs, nsa, k, qp, op, C.byref(bad)), bad)
+        return [int(x) for x in o[:k]]
+
+    def _sumcheck_verify_batch(self, fn, ptrs, ns, claimed_sums, proofs, flags):
+        k = len(ns)
+        nsa = (C.c_size_t * max(k, 1))(*[int(n) for n in ns])
+        cs, csp = self._cat_u64([claimed_sums])
+        r, rp = self._cat_u64([p[0] for p in proofs])
+        q, qp = self._cat_u64([p[1] for p in proofs])
+        fe, fep = self._cat_u64([[int(p[2]) for p in proofs]])
+        verd, vdp = _out_u8(k)
+        exp, ep = _out_u64(k)
+        orc, op = _out_u64(k)
+        rej, bad = C.c_size_t(0), C.c_size_t(0)
+        self.check_batch(fn(self.h, ptrs, nsa, k, csp, rp, qp, fep, int(flags), vdp, ep, op, C.byref(rej), C.byref(bad)), bad)
+        return verd[:k].copy(), [int(x) for x in exp[:k]], [int(x) for x in orc[:k]], rej.value
+
+    def sumcheck_verify_batch(self, tables, claimed_sums, proofs, flags=0):
+        """zigz_sumcheck_verify_batch: SumcheckVerifier.verify of proofs[i] = (rounds, point, final_eval) against claimed_sums[i],
+        the oracle being table i's multilinear extension.  flags: 0 evaluates at the point as given (the reference: honest
+        proofs of two or more variables are rejected in general), SUMCHECK_VERIFY_POINT_REVERSED at the reversed point (honest
+        proofs accept).  Returns (verdicts np.uint8, expected_evals, oracle_evals, n_rejected)."""
+        k = len(tables)
+        arrs = [_u64(t) for t in tables]
+        ptrs = (u64p * max(k, 1))(*[p for _, p in arrs])
+        return self._sumcheck_verify_batch(lib.zigz_sumcheck_verify_batch, ptrs, [len(t) for t in tables], claimed_sums, proofs, flags)
+
+    def dev_sumcheck_verify_batch(self, d_tables, ns, claimed_sums, proofs, flags=0):
+        """zigz_dev_sumcheck_verify_batch over device-resident tables (packed u32 canonical, 16-byte aligned)."""
+        ptrs = (vp * max(len(ns), 1))(*[int(d) for d in d_tables])
+        return self._sumcheck_verify_batch(lib.zigz_dev_sumcheck_verify_batch, ptrs, ns, claimed_sums, proofs, flags)
 
     def _merkle_batch_out(self, rc, bad, k, roots, heights, handle, ns, keep):
         self.check_batch(rc, bad)
