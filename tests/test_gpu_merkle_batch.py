@@ -118,17 +118,40 @@ def test_commit_open_batch_matches_oracle(ctx):
         if v and j % 2:
             pt[0] = (1 << v) + 12345 if (1 << v) + 12345 < P else P - 2  # point[0] >= 2^v: the index wraps
         points.append(pt)
-    res, b = ctx.merkle_commit_batch(tables)
+    # 2^16 values p - 1 at a random point: the largest exact sum the eight partials of a table can hold before the one reduction
+    logs.append(16)
+    tables.append(np.full(1 << 16, P - 1, dtype=np.uint64))
+    points.append([int(x) for x in rng.integers(0, P, size=16)])
+    other = [[int(x) for x in rng.integers(0, P, size=v)] for v in logs]  # a second point set
+    ns = [len(t) for t in tables]
+    b = db = None
+    d = DevTables(ctx, tables, extra_offset=1)  # sources that are only 4-byte aligned: the eval reads the handle's aligned copy
     try:
+        try:
+            assert d.ptrs[-1] % 16 == 4
+            res, b = ctx.merkle_commit_batch(tables)
+            dres, db = ctx.dev_merkle_commit_batch(d.ptrs, ns)
+        finally:
+            d.free()  # the batch owns a copy of the values
         got = ctx.commit_open_batch(b, points)
-        again = ctx.commit_open_batch(b, points)  # the accumulators are left zero
+        again = ctx.commit_open_batch(b, points)  # nothing is carried between calls: no word is zeroed, every one is written
+        got_other = ctx.commit_open_batch(b, other)
+        back = ctx.commit_open_batch(b, points)
+        dgot = ctx.commit_open_batch(db, points)
     finally:
-        b.deinit()
-    for t, pt, g, g2, r in zip(tables, points, got, again, res):
-        val, idx, sib, dirs, leaf = O.commit_open(P, t, pt)
+        for h in (b, db):
+            if h is not None:
+                h.deinit()
+    assert again == got
+    assert dres == res
+    for t, r in zip(tables, res):
         assert r == O.merkle_build(t)
-        assert (g["value"], g["index"], g["siblings"], g["directions"], g["leaf"]) == (val, idx, sib, dirs, leaf)
-        assert g2 == g
+    for pts, runs in ((points, (got, back, dgot)), (other, (got_other,))):
+        for i, (t, pt) in enumerate(zip(tables, pts)):
+            want = O.commit_open(P, t, pt)
+            for run in runs:
+                g = run[i]
+                assert (g["value"], g["index"], g["siblings"], g["directions"], g["leaf"]) == want
 
 
 def test_commit_open_batch_large_matches_single_calls(ctx):

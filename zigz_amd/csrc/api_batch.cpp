@@ -364,12 +364,6 @@ zigz_status table_check(size_t n, const void *table, bool dev, const uint64_t *f
     return ZIGZ_OK;
 }
 
-bool canonical(const uint64_t *v, size_t n) {
-    for (size_t j = 0; j < n; j++)
-        if (v[j] >= P) return false;
-    return true;
-}
-
 }  // namespace
 
 extern "C" zigz_status zigz_sumcheck_radix_run_batch(void *user, zigz_radix_batch_sums_fn block_sums, zigz_radix_batch_fold_fn fold,
@@ -412,23 +406,18 @@ extern "C" zigz_status zigz_sumcheck_prove_batch(zigz_ctx *ctx, const uint64_t *
     if (k == 0) return ZIGZ_OK;
     if (k > ZIGZ_BATCH_MAX || !tables || !ns || !rounds || !points || !final_evals) return ZIGZ_ERR_INVALID_ARGUMENT;
     ZIGZ_NOTHROW_BEGIN
-    size_t f = k, off = 0;
-    zigz_status fst = ZIGZ_OK;
-    for (size_t i = 0; i < k && f == k; i++) {
-        // (a non-power-of-two length fails before anything reads the table; a bad challenge only after the upload has checked
-        // the values -- both are NOT_CANONICAL at the same table then)
-        const zigz_status st = table_check(ns[i], tables[i], false, fixed_challenges ? fixed_challenges + off : nullptr);
-        if (st != ZIGZ_OK) { f = i; fst = st; }
-        else off += log2_floor(ns[i]);
-    }
-    if (f < k) {  // a table before the first failing one may hold a value >= p: the single calls would stop there first
-        for (size_t i = 0; i < f; i++)
-            if (!canonical(tables[i], ns[i])) return fail_at(bad_index, i, ZIGZ_ERR_NOT_CANONICAL);
-        return fail_at(bad_index, f, fst);
-    }
+    CHK(checks_in_call_order(tables, ns, k, bad_index, [&](size_t *f) -> zigz_status {
+        for (size_t i = 0, off = 0; i < k; i++) {
+            // (a non-power-of-two length fails before anything reads the table; a bad challenge only after the upload has checked
+            // the values -- both are NOT_CANONICAL at the same table then)
+            const zigz_status st = table_check(ns[i], tables[i], false, fixed_challenges ? fixed_challenges + off : nullptr);
+            if (st != ZIGZ_OK) return fail_at(f, i, st);
+            off += log2_floor(ns[i]);
+        }
+        return ZIGZ_OK;
+    }));
     // one upload of all tables (each 16-byte aligned in the workspace), one range check
-    std::vector<size_t> at(k + 1, 0);
-    for (size_t i = 0; i < k; i++) at[i + 1] = at[i] + ((ns[i] + 3) & ~(size_t)3);
+    const std::vector<size_t> at = packed_offsets(ns, k);
     std::vector<uint64_t> packed(at[k], 0);
     for (size_t i = 0; i < k; i++) memcpy(packed.data() + at[i], tables[i], ns[i] * 8);
     void *d32;

@@ -17,6 +17,7 @@
 #include <thread>
 #include <vector>
 
+#include "batch_host.hpp"
 #include "field.hpp"
 #include "host_hash.hpp"
 #include "host_parallel.hpp"
@@ -192,6 +193,8 @@ zigz_status lasso_mapping_check(const uint64_t *table, size_t table_rows, const 
 zigz_status build_trees(zigz_ctx *ctx, const uint32_t *d_vals, size_t val_stride, size_t n_values, size_t npad,
                                uint8_t *d_slab, size_t ncols, bool record = false, TreeRef *ref = nullptr);
 zigz_status keccak_times_collect(zigz_ctx *ctx);
+size_t mle_batch_fill(const uint32_t *const *d_tables, const size_t *ns, size_t k, const uint64_t *points, bool reversed,
+                      MleBatchTab *tab, uint32_t *f);
 extern std::atomic<int> g_sleep_wait;
 #pragma GCC visibility pop
 

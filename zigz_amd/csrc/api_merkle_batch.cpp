@@ -4,9 +4,10 @@
 // One call to zigz_merkle_commit costs two allocations, an upload with its own round trip, a leaf launch and one launch per
 // level, and another round trip for the root; a 2^10-leaf tree is ~2 K permutations, well under a microsecond of the chip, so
 // a caller committing many small tables pays almost only for that.  Here a batch makes one device allocation (descriptors,
-// values, trees and the eval accumulators of all k tables), one upload, ceil(max height / 9) build launches and one launch that
-// publishes the roots into pinned memory; an opening is one copy of descriptors, (an eval launch,) one path launch and one
-// hand-off.  Every tree is the dense tree of the single call, node for node, so roots and paths are byte-identical to it.
+// values, trees and the eval words of all k tables), one upload, ceil(max height / 9) build launches and one launch that
+// publishes the roots into pinned memory; an opening is one copy of descriptors, (the two launches of the batched MLE
+// evaluation, mle_batch.hip,) one path launch and one hand-off.  Every tree is the dense tree of the single call, node for
+// node, so roots and paths are byte-identical to it.
 #include "api_internal.hpp"
 
 #include <algorithm>
@@ -22,11 +23,13 @@ struct zigz_merkle_batch {
     std::vector<size_t> tree_off;  // nodes into d_tree (2 npad per tree)
     std::vector<size_t> sib_off;   // sum of the heights before the tree
     size_t sum_h;
-    void *d_mem;                   // the one allocation: descriptors | values | accumulators | trees
+    uint64_t max_n;                // the largest table
+    size_t eval_wgs;               // workgroups of the opening's eval launch: sum of ceil(n / MLE_BATCH_CHUNK)
+    void *d_mem;                   // the one allocation: descriptors | values | eval words | trees
     uint8_t *d_desc;
     size_t desc_bytes;
     uint32_t *d_vals;
-    unsigned long long *d_acc;     // k words, zero between calls
+    unsigned long long *d_eval;    // k results, then eval_wgs partial sums: an opening's launches write all of them, none is ever zeroed
     uint8_t *d_tree;
 };
 
@@ -36,7 +39,7 @@ constexpr size_t MAX_VALUES = (size_t)1 << 40;  // merkle_tree.zig:287 (the sing
 
 unsigned stages_of(unsigned h) { return h <= MB_STAGE_LEVELS ? 1 : (h + MB_STAGE_LEVELS - 1) / MB_STAGE_LEVELS; }
 size_t open_desc_bytes(size_t k, size_t sum_h) {
-    return align256(k * sizeof(MPathTab)) + align256(k * sizeof(MEvalTab)) + 2 * sum_h * sizeof(uint32_t);
+    return align256(k * sizeof(MPathTab)) + align256(k * sizeof(MleBatchTab)) + 2 * sum_h * sizeof(uint32_t);
 }
 
 // Narrows the host tables into the packed u32 staging (table i at word vals_off[i]) and finds the first table holding a
@@ -111,23 +114,25 @@ zigz_status commit_run(zigz_ctx *ctx, const uint32_t *const *d_values, const uin
     b->n.assign(ns, ns + k);
     b->npad.resize(k);
     b->height.resize(k);
-    b->vals_off.resize(k);
+    b->vals_off = packed_offsets(ns, k);
     b->tree_off.resize(k);
     b->sib_off.resize(k);
-    size_t vw = 0, nodes = 0, sum_h = 0;
+    size_t nodes = 0, sum_h = 0, eval_wgs = 0;
+    const size_t vw = b->vals_off[k];
     unsigned max_stages = 1;
     for (size_t i = 0; i < k; i++) {
         b->npad[i] = ceil_pow2(ns[i]);
         b->height[i] = log2_floor(b->npad[i]);
-        b->vals_off[i] = vw;
-        vw += (ns[i] + 3) & ~(size_t)3;
         b->tree_off[i] = nodes;
         nodes += 2 * b->npad[i];
         b->sib_off[i] = sum_h;
         sum_h += b->height[i];
+        eval_wgs += (ns[i] + MLE_BATCH_CHUNK - 1) / MLE_BATCH_CHUNK;
         max_stages = std::max(max_stages, stages_of(b->height[i]));
     }
     b->sum_h = sum_h;
+    b->eval_wgs = eval_wgs;
+    b->max_n = *std::max_element(ns, ns + k);
     // the descriptors of every stage, one block: stage s serves the trees that reach level 9 s + 1
     std::vector<MBatchTab> tabs;
     std::vector<size_t> st_first(max_stages + 1), st_wgs(max_stages);
@@ -155,7 +160,7 @@ zigz_status commit_run(zigz_ctx *ctx, const uint32_t *const *d_values, const uin
     }
     st_first[max_stages] = tabs.size();
     b->desc_bytes = align256(std::max(tabs.size() * sizeof(MBatchTab), open_desc_bytes(k, sum_h)));
-    const size_t vals_bytes = align256(vw * 4 + 16), acc_bytes = align256(k * 8);
+    const size_t vals_bytes = align256(vw * 4 + 16), eval_bytes = align256((k + eval_wgs) * 8);
     // pinned: roots | descriptors | (host form) values -- the last two go up in ONE copy, mirroring the device layout
     const size_t roots_bytes = align256(k * 32);
     const size_t up_bytes = b->desc_bytes + (values ? vw * 4 : 0);
@@ -174,16 +179,16 @@ zigz_status commit_run(zigz_ctx *ctx, const uint32_t *const *d_values, const uin
             return fail_at(bad_index, bad, ZIGZ_ERR_NOT_CANONICAL);
         }
     }
-    if (hipMalloc(&b->d_mem, b->desc_bytes + vals_bytes + acc_bytes + nodes * 32) != hipSuccess) {
+    if (hipMalloc(&b->d_mem, b->desc_bytes + vals_bytes + eval_bytes + nodes * 32) != hipSuccess) {
         (void)hipGetLastError();
-        set_err(ctx, "hipMalloc of %zu bytes for a batch of %zu trees failed", b->desc_bytes + vals_bytes + acc_bytes + nodes * 32, k);
+        set_err(ctx, "hipMalloc of %zu bytes for a batch of %zu trees failed", b->desc_bytes + vals_bytes + eval_bytes + nodes * 32, k);
         delete b;
         return ZIGZ_ERR_OUT_OF_MEMORY;
     }
     b->d_desc = (uint8_t *)b->d_mem;
     b->d_vals = (uint32_t *)(b->d_desc + b->desc_bytes);
-    b->d_acc = (unsigned long long *)((uint8_t *)b->d_vals + vals_bytes);
-    b->d_tree = (uint8_t *)b->d_acc + acc_bytes;
+    b->d_eval = (unsigned long long *)((uint8_t *)b->d_vals + vals_bytes);
+    b->d_tree = (uint8_t *)b->d_eval + eval_bytes;
     auto body = [&]() -> zigz_status {
         for (auto &t : tabs) {
             t.vals = b->d_vals + b->vals_off[t.idx];
@@ -192,7 +197,6 @@ zigz_status commit_run(zigz_ctx *ctx, const uint32_t *const *d_values, const uin
         }
         memcpy(h_up, tabs.data(), tabs.size() * sizeof(MBatchTab));
         HIPCHK(ctx, hipMemcpyAsync(b->d_desc, h_up, up_bytes, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(b->d_acc, 0, k * 8, ctx->stream));
         const MBatchTab *d_tabs = (const MBatchTab *)b->d_desc;
         launch_mbatch_subtrees(d_tabs, (unsigned)(st_first[1] - st_first[0]), (unsigned)st_wgs[0], ctx->stream);
         for (unsigned s = 1; s < max_stages; s++)
@@ -216,7 +220,7 @@ zigz_status commit_run(zigz_ctx *ctx, const uint32_t *const *d_values, const uin
     ZIGZ_NOTHROW_END(ctx)
 }
 
-// the openings of every tree at idx[i]; points != nullptr: CommitmentScheme.open (the eval first, into the accumulators)
+// the openings of every tree at idx[i]; points != nullptr: CommitmentScheme.open (the evals first, into the handle's result words)
 zigz_status open_run(zigz_ctx *ctx, const zigz_merkle_batch *b, const uint64_t *idx, const uint64_t *points, uint64_t *values,
                      uint8_t *siblings, uint8_t *dirs, uint64_t *leaf_values) {
     const size_t k = b->k, sum_h = b->sum_h;
@@ -232,40 +236,26 @@ zigz_status open_run(zigz_ctx *ctx, const zigz_merkle_batch *b, const uint64_t *
     o.value = (uint64_t *)(pin + sib_b + dir_b + leaf_b);
     uint8_t *h_up = pin + out_bytes;
     MPathTab *hp = (MPathTab *)h_up;
-    MEvalTab *he = (MEvalTab *)(h_up + align256(k * sizeof(MPathTab)));
-    const size_t f_off = align256(k * sizeof(MPathTab)) + align256(k * sizeof(MEvalTab));
-    uint32_t *hf = (uint32_t *)(h_up + f_off);
-    const uint32_t *d_f = (const uint32_t *)(b->d_desc + f_off);
-    size_t wg = 0;
+    const size_t e_off = align256(k * sizeof(MPathTab)), f_off = e_off + align256(k * sizeof(MleBatchTab));
+    std::vector<const uint32_t *> tables(k);
     for (size_t i = 0; i < k; i++) {
         MPathTab &p = hp[i];
-        p.vals = b->d_vals + b->vals_off[i];
+        p.vals = tables[i] = b->d_vals + b->vals_off[i];  // the handle's copy: 16-byte aligned whatever the caller's table was
         p.tree = b->d_tree + b->tree_off[i] * 32;
-        p.acc = points ? b->d_acc + i : nullptr;
+        p.acc = points ? (const uint64_t *)(b->d_eval + i) : nullptr;
         p.npad = b->npad[i];
         p.index = idx[i];
         p.sib_off = b->sib_off[i];
         p.height = b->height[i];
         p.idx = (uint32_t)i;
-        if (points) {
-            const unsigned nv = b->height[i];
-            const uint64_t *pt = points + b->sib_off[i];
-            for (unsigned v = 0; v < nv; v++) {  // eq factors of coordinate v (index bit v): 1 - r, r (Montgomery form)
-                hf[2 * (b->sib_off[i] + v)] = host_to_mont((1 + (uint64_t)P - pt[v]) % P);
-                hf[2 * (b->sib_off[i] + v) + 1] = host_to_mont(pt[v]);
-            }
-            MEvalTab &e = he[i];
-            e.vals = p.vals;
-            e.f = d_f + 2 * b->sib_off[i];
-            e.acc = b->d_acc + i;
-            e.n = b->n[i];
-            e.nv = nv;
-            e.first_wg = (uint32_t)wg;
-            wg += (b->n[i] + MB_EVAL_CHUNK - 1) / MB_EVAL_CHUNK;
-        }
     }
+    if (points) mle_batch_fill(tables.data(), b->n.data(), k, points, false, (MleBatchTab *)(h_up + e_off), (uint32_t *)(h_up + f_off));
     HIPCHK(ctx, hipMemcpyAsync(b->d_desc, h_up, points ? up_bytes : k * sizeof(MPathTab), hipMemcpyHostToDevice, ctx->stream));
-    if (points) launch_mbatch_eval((const MEvalTab *)(b->d_desc + align256(k * sizeof(MPathTab))), (unsigned)k, (unsigned)wg, ctx->stream);
+    if (points) {  // partial sums per workgroup, then table i's reduced result into d_eval[i]: device words, so nothing to signal
+        const MleBatchTab *d_tabs = (const MleBatchTab *)(b->d_desc + e_off);
+        launch_mle_batch_eval(d_tabs, (unsigned)k, (unsigned)b->eval_wgs, (const uint32_t *)(b->d_desc + f_off), b->d_eval + k, ctx->stream);
+        launch_mle_batch_finish(d_tabs, (unsigned)k, b->d_eval + k, (uint64_t *)b->d_eval, ctx->stream, DoneFlag());
+    }
     const DoneFlag done = done_flag(ctx, 2);
     launch_mbatch_paths((const MPathTab *)b->d_desc, (unsigned)k, o, ctx->stream, done);
     HIPCHK(ctx, hipGetLastError());
@@ -301,18 +291,13 @@ extern "C" zigz_status zigz_merkle_commit_batch(zigz_ctx *ctx, const uint64_t *c
     if (k == 0) return ZIGZ_OK;
     if (k > ZIGZ_BATCH_MAX || !values || !ns || !roots) return ZIGZ_ERR_INVALID_ARGUMENT;
     ZIGZ_NOTHROW_BEGIN
-    size_t f = k;
-    zigz_status fst = ZIGZ_OK;
-    for (size_t i = 0; i < k && f == k; i++) {
-        const zigz_status st = table_pre(ns[i], values[i], false);
-        if (st != ZIGZ_OK) { f = i; fst = st; }
-    }
-    if (f < k) {  // a table before the first failing one may hold a value >= p: the single calls would stop there first
-        for (size_t i = 0; i < f; i++)
-            for (size_t j = 0; j < ns[i]; j++)
-                if (values[i][j] >= P) return fail_at(bad_index, i, ZIGZ_ERR_NOT_CANONICAL);
-        return fail_at(bad_index, f, fst);
-    }
+    CHK(checks_in_call_order(values, ns, k, bad_index, [&](size_t *f) -> zigz_status {
+        for (size_t i = 0; i < k; i++) {
+            const zigz_status st = table_pre(ns[i], values[i], false);
+            if (st != ZIGZ_OK) return fail_at(f, i, st);
+        }
+        return ZIGZ_OK;
+    }));
     return commit_run(ctx, nullptr, values, ns, k, roots, heights, out, bad_index);  // (checks the values while it narrows them)
     ZIGZ_NOTHROW_END(ctx)
 }
@@ -334,6 +319,9 @@ extern "C" zigz_status zigz_commit_open_batch(zigz_ctx *ctx, const zigz_merkle_b
     ZIGZ_ENTER(ctx);
     if (!ctx || !b || b->ctx != ctx || !values || !indices || !leaf_values || (b->sum_h && (!points || !siblings || !dirs)))
         return ZIGZ_ERR_INVALID_ARGUMENT;
+    // k_mle_batch_eval sums exactly up to 2^MLE_BATCH_MAX_LOG2_N values per table in at most MLE_BATCH_MAX_WGS chunks.  A table
+    // of 2^33 values needs 32 GiB of values and 512 GiB of tree, 2^24 chunks are 2^37 values: no handle that large fits the device.
+    if (b->eval_wgs > MLE_BATCH_MAX_WGS || b->max_n > ((uint64_t)1 << MLE_BATCH_MAX_LOG2_N)) return ZIGZ_ERR_INVALID_ARGUMENT;
     ZIGZ_NOTHROW_BEGIN
     std::vector<uint64_t> idx(b->k);
     for (size_t i = 0; i < b->k; i++) {

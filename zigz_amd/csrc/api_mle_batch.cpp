@@ -13,53 +13,13 @@
 
 using namespace zk;
 
-namespace {
-
-// one call's pinned region: results (k u64) | descriptors | factors | the narrowed tables of the host forms
-struct Layout {
-    size_t k = 0, tot_v = 0, nwg = 0;
-    size_t desc_off = 0, f_off = 0, stage_bytes = 0, tab_off = 0, tab_words = 0, bytes = 0;
-    std::vector<size_t> at;  // host forms: table i's first word among the narrowed tables (every table 16-byte aligned)
-};
-
-// a host table's value >= p at table i: the same words in the context's last error whichever path found it
-zigz_status not_canonical(zigz_ctx *ctx, size_t *bad_index, size_t i) {
-    set_err(ctx, "input contains a value >= p (not a canonical BabyBear element)");
-    return fail_at(bad_index, i, ZIGZ_ERR_NOT_CANONICAL);
-}
-
-// ns[i] are powers of two <= 2^32 (checked by the callers)
-zigz_status plan(const size_t *ns, size_t k, bool host_tables, Layout &L) {
-    L.k = k;
-    for (size_t i = 0; i < k; i++) {
-        L.tot_v += log2_floor(ns[i]);
-        L.nwg += (ns[i] + MLE_BATCH_CHUNK - 1) / MLE_BATCH_CHUNK;
-    }
-    if (L.nwg > MLE_BATCH_MAX_WGS) return ZIGZ_ERR_INVALID_ARGUMENT;  // one launch: fewer than 2^32 threads in its grid
-    L.desc_off = align256(k * 8);
-    L.f_off = L.desc_off + align256(k * sizeof(MleBatchTab));
-    L.stage_bytes = L.f_off + align256(2 * L.tot_v * 4 + 4) - L.desc_off;
-    L.tab_off = L.desc_off + L.stage_bytes;
-    if (host_tables) {
-        L.at.assign(k + 1, 0);
-        for (size_t i = 0; i < k; i++) L.at[i + 1] = L.at[i] + ((ns[i] + 3) & ~(size_t)3);
-        L.tab_words = L.at[k];
-    }
-    L.bytes = L.tab_off + L.tab_words * 4;
-    return ZIGZ_OK;
-}
-
-// Queues the copy and the two launches; the k results arrive as u64 at the start of `pin` once `done` is published.
+// The k descriptors of one eval launch and the factor pairs of its points (1 - r and r, Montgomery form), pair i's at f + 2 (sum
+// of the variables before it); returns the launch's workgroup count.  points: the pairs' coordinates one behind the other.
 // reversed: index bit v is bound to the point's coordinate nv - 1 - v instead of v (the order of the descriptor's factors).
-zigz_status eval_queue(zigz_ctx *ctx, const Layout &L, uint8_t *pin, const uint32_t *const *d_tables, const size_t *ns,
-                       const uint64_t *points, bool reversed, DoneFlag *done) {
-    void *d_stage, *d_part;
-    CHK(ws_get(ctx, WS_MLEBATCH, L.stage_bytes, &d_stage));
-    CHK(ws_get(ctx, WS_MLEBATCH_PART, L.nwg * 8, &d_part));  // one partial sum per workgroup, all written by the launch
-    MleBatchTab *tab = (MleBatchTab *)(pin + L.desc_off);
-    uint32_t *f = (uint32_t *)(pin + L.f_off);
+size_t mle_batch_fill(const uint32_t *const *d_tables, const size_t *ns, size_t k, const uint64_t *points, bool reversed,
+                      MleBatchTab *tab, uint32_t *f) {
     size_t off = 0, wg = 0;
-    for (size_t i = 0; i < L.k; i++) {
+    for (size_t i = 0; i < k; i++) {
         const unsigned nv = log2_floor(ns[i]);
         MleBatchTab t{};
         t.vals = d_tables[i];
@@ -77,6 +37,53 @@ zigz_status eval_queue(zigz_ctx *ctx, const Layout &L, uint8_t *pin, const uint3
         off += nv;
         wg += (ns[i] + MLE_BATCH_CHUNK - 1) / MLE_BATCH_CHUNK;
     }
+    return wg;
+}
+
+namespace {
+
+// one call's pinned region: results (k u64) | descriptors | factors | the narrowed tables of the host forms
+struct Layout {
+    size_t k = 0, tot_v = 0, nwg = 0;
+    size_t desc_off = 0, f_off = 0, stage_bytes = 0, tab_off = 0, tab_words = 0, bytes = 0;
+    std::vector<size_t> at;  // host forms: table i's first word among the narrowed tables (every table 16-byte aligned)
+};
+
+// a host table's value >= p at table i: the same words in the context's last error whichever path found it
+constexpr const char *NOT_CANONICAL_TEXT = "input contains a value >= p (not a canonical BabyBear element)";
+
+zigz_status not_canonical(zigz_ctx *ctx, size_t *bad_index, size_t i) {
+    set_err(ctx, "%s", NOT_CANONICAL_TEXT);
+    return fail_at(bad_index, i, ZIGZ_ERR_NOT_CANONICAL);
+}
+
+// ns[i] are powers of two <= 2^32 (checked by the callers)
+zigz_status plan(const size_t *ns, size_t k, bool host_tables, Layout &L) {
+    L.k = k;
+    for (size_t i = 0; i < k; i++) {
+        L.tot_v += log2_floor(ns[i]);
+        L.nwg += (ns[i] + MLE_BATCH_CHUNK - 1) / MLE_BATCH_CHUNK;
+    }
+    if (L.nwg > MLE_BATCH_MAX_WGS) return ZIGZ_ERR_INVALID_ARGUMENT;  // one launch: fewer than 2^32 threads in its grid
+    L.desc_off = align256(k * 8);
+    L.f_off = L.desc_off + align256(k * sizeof(MleBatchTab));
+    L.stage_bytes = L.f_off + align256(2 * L.tot_v * 4 + 4) - L.desc_off;
+    L.tab_off = L.desc_off + L.stage_bytes;
+    if (host_tables) {
+        L.at = packed_offsets(ns, k);
+        L.tab_words = L.at[k];
+    }
+    L.bytes = L.tab_off + L.tab_words * 4;
+    return ZIGZ_OK;
+}
+
+// Queues the copy and the two launches; the k results arrive as u64 at the start of `pin` once `done` is published.
+zigz_status eval_queue(zigz_ctx *ctx, const Layout &L, uint8_t *pin, const uint32_t *const *d_tables, const size_t *ns,
+                       const uint64_t *points, bool reversed, DoneFlag *done) {
+    void *d_stage, *d_part;
+    CHK(ws_get(ctx, WS_MLEBATCH, L.stage_bytes, &d_stage));
+    CHK(ws_get(ctx, WS_MLEBATCH_PART, L.nwg * 8, &d_part));  // one partial sum per workgroup, all written by the launch
+    mle_batch_fill(d_tables, ns, L.k, points, reversed, (MleBatchTab *)(pin + L.desc_off), (uint32_t *)(pin + L.f_off));
     HIPCHK(ctx, hipMemcpyAsync(d_stage, pin + L.desc_off, L.stage_bytes, hipMemcpyHostToDevice, ctx->stream));
     *done = done_flag(ctx, 2);
     const uint8_t *ds = (const uint8_t *)d_stage;
@@ -94,7 +101,7 @@ zigz_status upload_tables(zigz_ctx *ctx, const Layout &L, uint8_t *pin, const ui
                           std::vector<const uint32_t *> &d, size_t *bad_index) {
     uint32_t *h = (uint32_t *)(pin + L.tab_off);
     for (size_t i = 0; i < L.k; i++)
-        if (!sv::narrow(tables[i], ns[i], h + L.at[i])) return not_canonical(ctx, bad_index, i);
+        if (!narrow(tables[i], ns[i], h + L.at[i])) return not_canonical(ctx, bad_index, i);
     void *d32;
     CHK(ws_get(ctx, WS_MLEBATCH_IN, L.tab_words * 4, &d32));
     HIPCHK(ctx, hipMemcpyAsync(d32, h, L.tab_words * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -103,17 +110,14 @@ zigz_status upload_tables(zigz_ctx *ctx, const Layout &L, uint8_t *pin, const ui
     return ZIGZ_OK;
 }
 
-// A host form's checks: the shapes and the proof words first; if a pair fails them, the values of every table before it (the
-// single calls, made in order, would stop at such a table first).  When all pass, upload_tables checks the values as it
-// narrows them, before anything is launched.
+// A host form's checks (batch_host.hpp: checks_in_call_order) with this file's error text for a value >= p.  When all pass,
+// upload_tables checks the values as it narrows them, before anything is launched.
 template <class Check>
 zigz_status host_checks(zigz_ctx *ctx, const uint64_t *const *tables, const size_t *ns, size_t k, size_t *bad_index, Check check) {
-    size_t f = k;
-    const zigz_status st = check(&f);
-    if (st == ZIGZ_OK || f == k) return st;  // (f == k: not about one pair)
-    for (size_t i = 0; i < f; i++)
-        if (!sv::canonical(tables[i], ns[i])) return not_canonical(ctx, bad_index, i);
-    return fail_at(bad_index, f, st);
+    bool value;
+    const zigz_status st = checks_in_call_order(tables, ns, k, bad_index, check, &value);
+    if (value) set_err(ctx, "%s", NOT_CANONICAL_TEXT);
+    return st;
 }
 
 zigz_status eval_batch(zigz_ctx *ctx, const uint32_t *const *d_tables, const uint64_t *const *h_tables, const size_t *ns, size_t k,

@@ -21,12 +21,6 @@ constexpr size_t VEC_MIN_HALF = 4096;  // vector path needs half % (4*TPB*UNROLL
 
 
 // ------------------------------------------------------------------ reductions
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 // Adds the block's (s0, s1) into sums[0], sums[1]: wave shuffle -> LDS -> one atomic pair per block.
 __device__ __forceinline__ void block_add2(unsigned long long s0, unsigned long long s1,
                                            unsigned long long *sums) {
@@ -170,11 +164,7 @@ constexpr int BS_INFLIGHT = ZK_BS_INFLIGHT;
 // k_block_sums 35.3 -> 31.4 us (0.64 -> 0.72 of 8 TB/s), k_radix_fold 34.4 -> 30.5 us (0.68 -> 0.76), one 2^24 table 14.4 ->
 // 13.3 us.  (-DZK_STREAM_PLAIN: the plain loads of rounds 1-3, for A/B.)
 #ifndef ZK_STREAM_PLAIN
-__device__ __forceinline__ uint4 zk_stream_load(const uint4 *q) {
-    const zk_v4u v = __builtin_nontemporal_load(reinterpret_cast<const zk_v4u *>(q));
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-#define ZK_STREAM_LOAD(q) zk_stream_load(q)
+#define ZK_STREAM_LOAD(q) stream_load(q)
 #else
 #define ZK_STREAM_LOAD(q) (*(q))
 #endif

@@ -478,7 +478,6 @@ void launch_batch_fingerprints(const FpTab *d_tabs, unsigned nt, unsigned nwg, h
 // computes the levels above each block in LDS -- so a batch takes ceil(height / 9) launches for its highest tree, whatever k is.
 constexpr unsigned MB_BLOCK = 512;
 constexpr unsigned MB_STAGE_LEVELS = 9;  // log2(MB_BLOCK)
-constexpr unsigned MB_EVAL_CHUNK = 4096;  // values per workgroup of the batched eval
 struct MBatchTab {  // one tree in one stage; the workgroups of tree j are [first_wg, first_wg of tree j + 1)
     const uint32_t *src;  // stage 0: the values to hash (the caller's device table, or the handle's own copy)
     uint32_t *vals;       // the handle's copy of the values: stage 0 writes it when src != vals
@@ -490,20 +489,13 @@ struct MBatchTab {  // one tree in one stage; the workgroups of tree j are [firs
     uint32_t idx;         // the tree's position in the batch
     uint64_t reserved;
 };
-struct MPathTab {  // one opening: tree.open(index) (and the eval computed into *acc before, if acc != nullptr)
+struct MPathTab {  // one opening: tree.open(index) (and the table's evaluation, computed before, if acc != nullptr)
     const uint32_t *vals;
     const uint8_t *tree;
-    unsigned long long *acc;  // the batched eval's exact sum (left zero), or nullptr
+    const uint64_t *acc;      // the table's eval, reduced mod p (written by k_mle_batch_finish in front of the path launch), or nullptr
     uint64_t npad, index;
     uint64_t sib_off;         // siblings at h_sib + 32 sib_off, directions at h_dirs + sib_off
     uint32_t height, idx;
-};
-struct MEvalTab {  // eval(point) of one power-of-two table: sum_i T[i] prod_v f[2 v + bit v of i]  (exact, into *acc)
-    const uint32_t *vals;
-    const uint32_t *f;        // 2 nv Montgomery-form factors: (1 - r_v), r_v
-    unsigned long long *acc;
-    uint64_t n;
-    uint32_t nv, first_wg;
 };
 struct MPathOut {  // where the openings go (pinned host memory)
     uint8_t *sib, *dirs;
@@ -512,7 +504,6 @@ struct MPathOut {  // where the openings go (pinned host memory)
 void launch_mbatch_subtrees(const MBatchTab *d_tabs, unsigned nt, unsigned nwg, hipStream_t s);
 void launch_mbatch_level(const MBatchTab *d_tabs, unsigned nt, unsigned nwg, hipStream_t s);
 void launch_mbatch_roots(const MBatchTab *d_tabs, unsigned nt, uint8_t *h_roots, hipStream_t s, DoneFlag done);
-void launch_mbatch_eval(const MEvalTab *d_tabs, unsigned nt, unsigned nwg, hipStream_t s);
 void launch_mbatch_paths(const MPathTab *d_tabs, unsigned nt, const MPathOut &out, hipStream_t s, DoneFlag done);
 // Many openings of a batch's trees in one launch (zigz_merkle_open_many): the work item is 16 bytes of one sibling digest, the
 // lanes follow the OUTPUT (consecutive lanes store consecutive 16 bytes of the packed siblings) and gather from the trees.
@@ -572,8 +563,9 @@ struct MleBatchTab {  // one pair; its workgroups are [first_wg, first_wg of pai
 // part: one exact u64 partial sum per workgroup of the launch (nwg words, all written)
 void launch_mle_batch_eval(const MleBatchTab *d_tabs, unsigned nt, unsigned nwg, const uint32_t *d_f, unsigned long long *d_part,
                            hipStream_t s);
-// one workgroup per pair: its partials added, reduced mod p once, into pinned h_out[slot] (u64); completion signalled under `done`
-void launch_mle_batch_finish(const MleBatchTab *d_tabs, unsigned nt, const unsigned long long *d_part, uint64_t *h_out, hipStream_t s,
+// one workgroup per pair: its partials added, reduced mod p once, into out[slot] (u64) -- pinned host memory with completion
+// signalled under `done`, or device memory read by a later launch of the stream (done = DoneFlag(): nothing is signalled)
+void launch_mle_batch_finish(const MleBatchTab *d_tabs, unsigned nt, const unsigned long long *d_part, uint64_t *out, hipStream_t s,
                              DoneFlag done);
 
 }  // namespace zk

@@ -11,6 +11,10 @@
 // is complete after stage 0; a batch needs ceil(height / 9) stages for its highest tree, however many trees it holds.
 // Digests stay in the tree form of keccak.hpp and become canonical bytes only where they leave the device (roots, paths).
 //
+// An opening is one wave per tree (k_mbatch_paths).  A CommitmentScheme opening evaluates the tables first with the batched
+// MLE kernels (mle_batch.hip: k_mle_batch_eval, k_mle_batch_finish) into result words in the handle, which the path launch
+// copies out: this file has no evaluation of its own.
+//
 // Results reach the host through pinned memory: every workgroup of a publishing launch writes its share, fences system-wide
 // and passes a barrier BEFORE it counts itself (signal_done_block, tree_dev.hpp); the last one stores the completion word.
 #include "kernels.hpp"
@@ -22,27 +26,8 @@ namespace zk {
 
 static_assert(MB_BLOCK == 1u << MB_STAGE_LEVELS, "a stage's block spans its levels");
 static_assert(MB_BLOCK == 2 * TPB, "a stage-0 workgroup hashes two leaves per thread");
-static_assert(MB_EVAL_CHUNK == 16 * TPB, "the eval's index bits: 8 from the lane, 4 from the loop, the rest uniform");
 
 namespace {
-
-// the descriptor that owns workgroup `wg`: the last one whose first workgroup is <= wg
-template <class T>
-__device__ __forceinline__ unsigned mb_find(const T *__restrict__ tabs, unsigned nt, unsigned wg) {
-    unsigned lo = 0, hi = nt;
-    while (hi - lo > 1) {
-        const unsigned mid = (lo + hi) >> 1;
-        if (tabs[mid].first_wg <= wg) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ unsigned long long mb_wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
 
 // The levels above a block of `cnt` digests (a power of two <= MB_BLOCK) of level l that sit in A; the block's first node is
 // node `base` of level l.  Ping-pong between A and B: a level reads one buffer and writes the other, so one barrier per level
@@ -73,7 +58,7 @@ __device__ __forceinline__ void mb_levels(Digest *A, Digest *B, uint8_t *tree, s
 __global__ __launch_bounds__(TPB) void k_mbatch_subtrees(const MBatchTab *__restrict__ tabs, unsigned nt) {
     __shared__ __align__(16) Digest A[MB_BLOCK];
     __shared__ __align__(16) Digest B[MB_BLOCK / 2];
-    const MBatchTab &d = tabs[mb_find(tabs, nt, blockIdx.x)];
+    const MBatchTab &d = tabs[find_first_wg(tabs, nt, blockIdx.x)];
     const size_t base = (size_t)(blockIdx.x - d.first_wg) * MB_BLOCK;
     const unsigned cnt = (unsigned)(d.npad - base < MB_BLOCK ? d.npad - base : MB_BLOCK);
     const bool copy = d.src != d.vals;
@@ -98,7 +83,7 @@ __global__ __launch_bounds__(TPB) void k_mbatch_subtrees(const MBatchTab *__rest
 __global__ __launch_bounds__(TPB) void k_mbatch_level(const MBatchTab *__restrict__ tabs, unsigned nt) {
     __shared__ __align__(16) Digest A[MB_BLOCK];
     __shared__ __align__(16) Digest B[MB_BLOCK / 2];
-    const MBatchTab &d = tabs[mb_find(tabs, nt, blockIdx.x)];
+    const MBatchTab &d = tabs[find_first_wg(tabs, nt, blockIdx.x)];
     const size_t n_in = d.npad >> d.lin, base = (size_t)(blockIdx.x - d.first_wg) * MB_BLOCK;
     const unsigned cnt = (unsigned)(n_in - base < MB_BLOCK ? n_in - base : MB_BLOCK);
     const uint4 *g = reinterpret_cast<const uint4 *>(d.tree + (slab_level_offset(d.npad, d.lin) + base) * 32);
@@ -121,46 +106,15 @@ __global__ __launch_bounds__(TPB) void k_mbatch_roots(const MBatchTab *__restric
     signal_done_block(done, gridDim.x);  // (TPB threads: several waves; no thread returns early)
 }
 
-// eval(point) of every table (multilinear.zig:110-144: index bit v selects r_v or 1 - r_v), exact: each term is a canonical
-// product < p, a table's 2^v terms add up below 2^(31 + v) in the u64 *acc.  Index i = base + 256 j + lane: bits 0-7 are the
-// lane's, 8-11 the loop's, the rest the workgroup's, so each weight costs at most four products more than the term.
-__global__ __launch_bounds__(TPB) void k_mbatch_eval(const MEvalTab *__restrict__ tabs, unsigned nt) {
-    ZK_PRIO_SMALL();
-    const MEvalTab &d = tabs[mb_find(tabs, nt, blockIdx.x)];
-    const size_t base = (size_t)(blockIdx.x - d.first_wg) * MB_EVAL_CHUNK;
-    const unsigned t = threadIdx.x, nv = d.nv;
-    uint32_t w_hi = R_MOD_P, w_lo = R_MOD_P;  // Montgomery form of 1
-#pragma unroll 1
-    for (unsigned v = 12; v < nv; v++) w_hi = mont_mul(w_hi, d.f[2 * v + ((base >> v) & 1)]);
-#pragma unroll 1
-    for (unsigned v = 0; v < 8 && v < nv; v++) w_lo = mont_mul(w_lo, d.f[2 * v + ((t >> v) & 1)]);
-    const uint32_t w0 = mont_mul(w_hi, w_lo);
-    unsigned long long acc = 0;
-#pragma unroll 1
-    for (unsigned j = 0; j < MB_EVAL_CHUNK / TPB; j++) {
-        const size_t i = base + (size_t)j * TPB + t;
-        if (i < d.n) {
-            uint32_t w = w0;
-            for (unsigned v = 8; v < 12 && v < nv; v++) w = mont_mul(w, d.f[2 * v + ((j >> (v - 8)) & 1)]);
-            acc += mont_mul(w, d.vals[i]);  // Montgomery weight x canonical value -> canonical product
-        }
-    }
-    acc = mb_wave_sum(acc);
-    if ((t & 63) == 0 && acc) atomicAdd(d.acc, acc);
-}
-
-// tree.open(index) of every tree (merkle_tree.zig:324-360), one wave per tree, lane l for level l; the paths, leaves and (after
-// k_mbatch_eval) the evaluations go straight into pinned memory.
+// tree.open(index) of every tree (merkle_tree.zig:324-360), one wave per tree, lane l for level l; the paths, the leaves and
+// the evaluations (reduced results of k_mle_batch_finish, queued in front of this launch) go straight into pinned memory.
 __global__ __launch_bounds__(64) void k_mbatch_paths(const MPathTab *__restrict__ tabs, unsigned nt, MPathOut out, DoneFlag done) {
     ZK_PRIO_SMALL();
     const MPathTab &d = tabs[blockIdx.x];
     const unsigned l = threadIdx.x;
     if (l == 0) {
         out.leaf[d.idx] = d.vals[d.index];
-        if (d.acc) {
-            out.value[d.idx] = *d.acc % P;
-            *d.acc = 0;  // left zero for the next opening
-        }
+        if (d.acc) out.value[d.idx] = *d.acc;
     }
     if (l < d.height) {
         const size_t ci = d.index >> l;  // current_index at level l
@@ -240,9 +194,6 @@ void launch_mbatch_level(const MBatchTab *d_tabs, unsigned nt, unsigned nwg, hip
 }
 void launch_mbatch_roots(const MBatchTab *d_tabs, unsigned nt, uint8_t *h_roots, hipStream_t s, DoneFlag done) {
     hipLaunchKernelGGL(k_mbatch_roots, dim3((nt + TPB - 1) / TPB), dim3(TPB), 0, s, d_tabs, nt, h_roots, done);
-}
-void launch_mbatch_eval(const MEvalTab *d_tabs, unsigned nt, unsigned nwg, hipStream_t s) {
-    hipLaunchKernelGGL(k_mbatch_eval, dim3(nwg), dim3(TPB), 0, s, d_tabs, nt);
 }
 void launch_mbatch_paths(const MPathTab *d_tabs, unsigned nt, const MPathOut &out, hipStream_t s, DoneFlag done) {
     hipLaunchKernelGGL(k_mbatch_paths, dim3(nt), dim3(64), 0, s, d_tabs, nt, out, done);

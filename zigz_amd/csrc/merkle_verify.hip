@@ -25,16 +25,6 @@ static_assert(MV_TPB == TPB, "the host sizes the grid in workgroups of TPB threa
 
 namespace {
 
-__device__ __forceinline__ unsigned mv_find(const MVerifyTab *__restrict__ tabs, unsigned nt, unsigned wg) {
-    unsigned lo = 0, hi = nt;
-    while (hi - lo > 1) {
-        const unsigned mid = (lo + hi) >> 1;
-        if (tabs[mid].first_wg <= wg) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // canonical SHA3 bytes (4 little-endian u64 lanes) -> tree form: even bits of each lane in the low word, odd bits in the high
 // word (the inverse of canonical_digest)
 __device__ __forceinline__ uint64_t tree_lane(uint64_t x) {
@@ -55,7 +45,7 @@ __device__ __forceinline__ Digest load_tree_form(const uint8_t *p) {
 // the re-arm pauses, for launches that fill the chip.
 template <bool DEV, bool PAUSE>
 __global__ __launch_bounds__(TPB) void k_mverify(const MVerifyTab *__restrict__ tabs, unsigned nt, MVerifyArgs a) {
-    const MVerifyTab &t = tabs[mv_find(tabs, nt, blockIdx.x)];
+    const MVerifyTab &t = tabs[find_first_wg(tabs, nt, blockIdx.x)];
     const unsigned i = (blockIdx.x - t.first_wg) * TPB + threadIdx.x;  // lane within the bucket
     const bool active = i < t.cnt;
     bool ok = true;

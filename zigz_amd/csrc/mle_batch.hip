@@ -20,9 +20,11 @@
 // one -- are added in u64: a shuffle sum per wave, the four waves through LDS, and ONE plain store per workgroup into a
 // partial array indexed by the workgroup's number (no atomics: with one accumulator per pair the 512 .. 2048 waves of a
 // 2^20 .. 2^22 table queued up behind one cache line, and the launch ran at a tenth of the HBM rate).  k_mle_batch_finish, one
-// workgroup per pair, adds the pair's partials, reduces mod p ONCE and writes the result into pinned memory, then signals the
-// host (signal_done_block: fence, barrier, then count).  With n <= 2^MLE_BATCH_MAX_LOG2_N a pair's sum stays below
-// 2^31 * n <= 2^63 and cannot wrap.  Every partial is written by every launch, so nothing has to be zeroed between calls.
+// workgroup per pair, adds the pair's partials, reduces mod p ONCE and writes the result at the pair's slot: into pinned memory,
+// signalling the host afterwards (signal_done_block: fence, barrier, then count), or, for a batch opening
+// (zigz_commit_open_batch), into device words that the path launch behind it reads, signalling nothing.  With
+// n <= 2^MLE_BATCH_MAX_LOG2_N a pair's sum stays below 2^31 * n <= 2^63 and cannot wrap.  Every partial is written by every
+// launch, so nothing has to be zeroed between calls.
 #include "kernels.hpp"
 
 #include "field.hpp"
@@ -39,22 +41,6 @@ static_assert(TPB == 256, "A and B cover the thread's 8 index bits, wave 1 the h
 static_assert(31 + MLE_BATCH_MAX_LOG2_N < 64, "a pair's exact u64 sum: fewer than n terms below p < 2^31");
 static_assert(ME_HI_BIT + 64 > MLE_BATCH_MAX_LOG2_N, "one wave holds a factor per high variable");
 
-__device__ __forceinline__ uint4 me_stream_load(const uint4 *q) {
-    const zk_v4u v = __builtin_nontemporal_load(reinterpret_cast<const zk_v4u *>(q));
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-// the pair that owns workgroup `wg`: the last one whose first workgroup is <= wg
-__device__ __forceinline__ unsigned me_find(const MleBatchTab *__restrict__ tabs, unsigned nt, unsigned wg) {
-    unsigned lo = 0, hi = nt;
-    while (hi - lo > 1) {
-        const unsigned mid = (lo + hi) >> 1;
-        if (tabs[mid].first_wg <= wg) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // prod_{i < cnt} f_{v0 + i}[bit i of bits], Montgomery form; a variable the table does not have contributes (1, 0)
 __device__ __forceinline__ uint32_t me_eq(const uint32_t *__restrict__ f, unsigned nv, unsigned v0, unsigned cnt, unsigned bits) {
     uint32_t w = R_MOD_P;
@@ -65,12 +51,6 @@ __device__ __forceinline__ uint32_t me_eq(const uint32_t *__restrict__ f, unsign
     return w;
 }
 
-__device__ __forceinline__ unsigned long long me_wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(TPB) void k_mle_batch_eval(const MleBatchTab *__restrict__ tabs, unsigned nt,
@@ -79,7 +59,7 @@ __global__ __launch_bounds__(TPB) void k_mle_batch_eval(const MleBatchTab *__res
     __shared__ __align__(16) uint32_t s_u[4 * ME_LOADS];
     __shared__ uint32_t s_a[16], s_b[16], s_hi;
     __shared__ unsigned long long s_sum[TPB / 64];
-    const MleBatchTab d = tabs[me_find(tabs, nt, blockIdx.x)];
+    const MleBatchTab d = tabs[find_first_wg(tabs, nt, blockIdx.x)];
     const uint32_t *f = factors + d.f_off;
     const unsigned t = threadIdx.x, nv = d.nv;
     const size_t base = (size_t)(blockIdx.x - d.first_wg) * MLE_BATCH_CHUNK;
@@ -106,7 +86,7 @@ __global__ __launch_bounds__(TPB) void k_mle_batch_eval(const MleBatchTab *__res
 #pragma unroll
         for (int j = 0; j < ME_LOADS; j++) {
             const size_t q = q0 + (size_t)j * TPB + t;
-            v[j] = me_stream_load(p + (q < nq ? q : q0));  // clamped, not branched: the loads are issued back to back
+            v[j] = stream_load(p + (q < nq ? q : q0));  // clamped, not branched: the loads are issued back to back
         }
 #pragma unroll
         for (int j = 0; j < ME_LOADS; j++) {
@@ -130,26 +110,27 @@ __global__ __launch_bounds__(TPB) void k_mle_batch_eval(const MleBatchTab *__res
     const uint32_t s = monty_reduce(hi + monty_reduce(lo));
     const uint32_t w = mont_mul(mont_mul(s_a[t & 15], s_b[t >> 4]), s_hi);  // A B H R^2
     unsigned long long term = mont_mul(w, s);                               // canonical, < p
-    term = me_wave_sum(term);
+    term = wave_sum(term);
     if ((t & 63) == 0) s_sum[t >> 6] = term;
     __syncthreads();
     if (t == 0) part[blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
 }
 
 // One workgroup per pair: the pair's partial sums (one per workgroup of the eval launch, consecutive) added up, reduced mod p
-// once and written into pinned memory at the pair's result slot.
+// once and written at the pair's result slot: pinned memory (zigz_[dev_]mle_eval_batch, the sumcheck verifier) or the device
+// words a batch opening's path launch reads (zigz_commit_open_batch, which signals nothing here: done.flag is null).
 __global__ __launch_bounds__(TPB) void k_mle_batch_finish(const MleBatchTab *__restrict__ tabs, const unsigned long long *__restrict__ part,
-                                                          uint64_t *h_out, DoneFlag done) {
+                                                          uint64_t *out, DoneFlag done) {
     __shared__ unsigned long long s_sum[TPB / 64];
     const MleBatchTab d = tabs[blockIdx.x];
     const size_t cnt = (size_t)((d.n + MLE_BATCH_CHUNK - 1) / MLE_BATCH_CHUNK);
     const unsigned long long *p = part + d.first_wg;
     unsigned long long sum = 0;
     for (size_t j = threadIdx.x; j < cnt; j += TPB) sum += p[j];
-    sum = me_wave_sum(sum);
+    sum = wave_sum(sum);
     if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = sum;
     __syncthreads();
-    if (threadIdx.x == 0) h_out[d.slot] = (s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]) % (unsigned long long)P;
+    if (threadIdx.x == 0) out[d.slot] = (s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]) % (unsigned long long)P;
     signal_done_block(done, gridDim.x);  // (TPB threads: several waves; no thread returns early)
 }
 
@@ -157,9 +138,9 @@ void launch_mle_batch_eval(const MleBatchTab *d_tabs, unsigned nt, unsigned nwg,
                            hipStream_t s) {
     hipLaunchKernelGGL(k_mle_batch_eval, dim3(nwg), dim3(TPB), 0, s, d_tabs, nt, d_f, d_part);
 }
-void launch_mle_batch_finish(const MleBatchTab *d_tabs, unsigned nt, const unsigned long long *d_part, uint64_t *h_out, hipStream_t s,
+void launch_mle_batch_finish(const MleBatchTab *d_tabs, unsigned nt, const unsigned long long *d_part, uint64_t *out, hipStream_t s,
                              DoneFlag done) {
-    hipLaunchKernelGGL(k_mle_batch_finish, dim3(nt), dim3(TPB), 0, s, d_tabs, d_part, h_out, done);
+    hipLaunchKernelGGL(k_mle_batch_finish, dim3(nt), dim3(TPB), 0, s, d_tabs, d_part, out, done);
 }
 
 }  // namespace zk

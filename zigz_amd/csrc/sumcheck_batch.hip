@@ -25,28 +25,6 @@ constexpr int B_INFLIGHT = 4;  // 16-byte loads in flight per lane in the block-
 constexpr int B_RB = 16;       // rows per chunk of the fold (k_radix_fold: RB)
 constexpr int B_RLOOPS = 4;    // chunks per thread (k_radix_fold: RLOOPS) -> 64 rows per workgroup row-group
 
-__device__ __forceinline__ uint4 b_stream_load(const uint4 *q) {
-    const zk_v4u v = __builtin_nontemporal_load(reinterpret_cast<const zk_v4u *>(q));
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-__device__ __forceinline__ unsigned long long b_wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// the table that owns workgroup `wg`: the last one whose first workgroup is <= wg
-__device__ __forceinline__ unsigned b_find(const BatchTab *__restrict__ tabs, unsigned nt, unsigned wg) {
-    unsigned lo = 0, hi = nt;
-    while (hi - lo > 1) {
-        const unsigned mid = (lo + hi) >> 1;
-        if (tabs[mid].first_wg <= wg) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 template <bool FULL>
 __device__ __forceinline__ void b_fold_rows(const uint4 *p, const uint32_t *__restrict__ w, size_t mq, size_t nb, size_t gy,
                                             unsigned long long lo[4], unsigned long long hi[4]) {
@@ -56,7 +34,7 @@ __device__ __forceinline__ void b_fold_rows(const uint4 *p, const uint32_t *__re
         if (!FULL && b0 >= nb) break;
         uint4 v[B_RB];
 #pragma unroll
-        for (int j = 0; j < B_RB; j++) v[j] = b_stream_load(p + (FULL || b0 + j < nb ? b0 + j : nb - 1) * mq);
+        for (int j = 0; j < B_RB; j++) v[j] = stream_load(p + (FULL || b0 + j < nb ? b0 + j : nb - 1) * mq);
 #pragma unroll
         for (int j = 0; j < B_RB; j++) {
             const uint32_t wj = FULL ? w[b0 + j] : (w[b0 + j < nb ? b0 + j : nb - 1] & (b0 + j < nb ? ~0u : 0u));
@@ -88,7 +66,7 @@ __device__ __forceinline__ uint64_t b_xxh3_64_of_u64(uint64_t h) {
 // Pass 1 of a stage: the 2^k exact block sums of every table.  A wave reads iters x 64 16-byte chunks inside one block and
 // adds one partial sum; the pass's sums of all tables are one contiguous array (k_batch_publish hands it to the host).
 __global__ __launch_bounds__(TPB) void k_batch_block_sums(const BatchTab *__restrict__ tabs, unsigned nt) {
-    const BatchTab &d = tabs[b_find(tabs, nt, blockIdx.x)];
+    const BatchTab &d = tabs[find_first_wg(tabs, nt, blockIdx.x)];
     const unsigned lane = threadIdx.x & 63;
     const size_t wave = (size_t)(blockIdx.x - d.first_wg) * (TPB / 64) + (threadIdx.x >> 6);
     const unsigned iters = d.iters;
@@ -101,12 +79,12 @@ __global__ __launch_bounds__(TPB) void k_batch_block_sums(const BatchTab *__rest
         for (unsigned it = 0; it < iters; it += B_INFLIGHT) {
             uint4 a[B_INFLIGHT];
 #pragma unroll
-            for (int j = 0; j < B_INFLIGHT; j++) a[j] = b_stream_load(p + (size_t)(it + j < iters ? it + j : iters - 1) * 64);
+            for (int j = 0; j < B_INFLIGHT; j++) a[j] = stream_load(p + (size_t)(it + j < iters ? it + j : iters - 1) * 64);
 #pragma unroll
             for (int j = 0; j < B_INFLIGHT; j++)
                 acc += it + j < iters ? (unsigned long long)a[j].x + a[j].y + a[j].z + a[j].w : 0ull;
         }
-        acc = b_wave_sum(acc);
+        acc = wave_sum(acc);
         if (lane == 0 && acc) atomicAdd(&d.sums[(c0 * 4) >> (d.log2_n - d.k)], acc);
     }
 }
@@ -114,7 +92,7 @@ __global__ __launch_bounds__(TPB) void k_batch_block_sums(const BatchTab *__rest
 // Pass 2a: part[g][i] = sum over the g-th group of 64 rows b of W[b] * T[b*m + i]  (exact u64, m = n / 2^k), as k_radix_fold.
 __global__ __launch_bounds__(TPB) void k_batch_fold(const BatchTab *__restrict__ tabs, unsigned nt) {
     ZK_PRIO_SMALL();
-    const BatchTab &d = tabs[b_find(tabs, nt, blockIdx.x)];
+    const BatchTab &d = tabs[find_first_wg(tabs, nt, blockIdx.x)];
     const size_t m = (size_t)1 << (d.log2_n - d.k), nb = (size_t)1 << d.k, mq = m / 4;
     const size_t gx = (mq + TPB - 1) / TPB;
     const size_t local = blockIdx.x - d.first_wg, gy = local / gx;
@@ -136,7 +114,7 @@ __global__ __launch_bounds__(TPB) void k_batch_fold(const BatchTab *__restrict__
 // the 64 outputs of a wave fall into one block).  The next stage's sums of all tables form one contiguous array.
 __global__ __launch_bounds__(TPB) void k_batch_finalize(const BatchTab *__restrict__ tabs, unsigned nt) {
     ZK_PRIO_SMALL();
-    const BatchTab &d = tabs[b_find(tabs, nt, blockIdx.x)];
+    const BatchTab &d = tabs[find_first_wg(tabs, nt, blockIdx.x)];
     const size_t m = (size_t)1 << (d.log2_n - d.k), groups = ((size_t)1 << d.k) > (size_t)B_RB * B_RLOOPS
                                                                    ? ((size_t)1 << d.k) / ((size_t)B_RB * B_RLOOPS) : 1;
     const size_t i = (size_t)(blockIdx.x - d.first_wg) * TPB + threadIdx.x;
@@ -149,7 +127,7 @@ __global__ __launch_bounds__(TPB) void k_batch_finalize(const BatchTab *__restri
         d.out[i] = v;
     }
     if (d.log2_m2) {  // uniform over the workgroup (one table per workgroup)
-        const unsigned long long t = b_wave_sum((unsigned long long)v);
+        const unsigned long long t = wave_sum((unsigned long long)v);
         if ((threadIdx.x & 63) == 0 && i < m && t) atomicAdd(&d.sums[i >> d.log2_m2], t);
     }
 }
@@ -181,7 +159,7 @@ __global__ __launch_bounds__(TPB) void k_batch_publish(BatchPublish pub) {
 // The remaining tables (<= 1024 values each) into pinned memory, u32, table j's at pub.h_dst + tail_off words: every workgroup
 // writes its share, fences system-wide and passes a barrier before it counts itself; the last one stores the completion word.
 __global__ __launch_bounds__(TPB) void k_batch_tails(const BatchTab *__restrict__ tabs, unsigned nt, BatchPublish pub) {
-    const BatchTab &d = tabs[b_find(tabs, nt, blockIdx.x)];
+    const BatchTab &d = tabs[find_first_wg(tabs, nt, blockIdx.x)];
     const size_t m = (size_t)1 << d.log2_n;
     const size_t i = (size_t)(blockIdx.x - d.first_wg) * TPB + threadIdx.x;
     if (i < m) reinterpret_cast<uint32_t *>(pub.h_dst)[d.tail_off + i] = d.in[i];
@@ -191,13 +169,7 @@ __global__ __launch_bounds__(TPB) void k_batch_tails(const BatchTab *__restrict_
 // Lasso fingerprints of several instances' rows in one launch (k_lasso_fingerprints per row, per-instance widths): table t's
 // rows at in, its fingerprints at out; rows past `rows` up to the padded count are written as 0 (lasso_prover.zig:139-142).
 __global__ __launch_bounds__(TPB) void k_batch_fingerprints(const FpTab *__restrict__ tabs, unsigned nt) {
-    unsigned lo = 0, hi = nt;
-    while (hi - lo > 1) {
-        const unsigned mid = (lo + hi) >> 1;
-        if (tabs[mid].first_wg <= blockIdx.x) lo = mid;
-        else hi = mid;
-    }
-    const FpTab &d = tabs[lo];
+    const FpTab &d = tabs[find_first_wg(tabs, nt, blockIdx.x)];
     const size_t i = (size_t)(blockIdx.x - d.first_wg) * TPB + threadIdx.x;
     if (i >= d.padded) return;
     if (i >= d.rows) {

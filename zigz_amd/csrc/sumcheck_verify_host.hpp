@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "batch_host.hpp"  // canonical()
 #include "host_hash.hpp"
 #include "zigz_hip.h"
 
@@ -18,11 +19,6 @@ constexpr unsigned SV_MAX_LOG2_N = 32;  // the batched eval's exact u64 sum: 2^3
 inline uint64_t f_add(uint64_t a, uint64_t b) { const uint64_t s = a + b; return s >= SV_P ? s - SV_P : s; }
 inline uint64_t f_mul(uint64_t a, uint64_t b) { return (uint64_t)(((unsigned __int128)a * b) % SV_P); }
 inline unsigned log2_of(size_t n) { unsigned l = 0; while (n > 1) { n >>= 1; l++; } return l; }
-inline bool canonical(const uint64_t *v, size_t n) {
-    for (size_t j = 0; j < n; j++)
-        if (v[j] >= SV_P) return false;
-    return true;
-}
 inline zigz_status bad_at(size_t *bad_index, size_t i, zigz_status st) {
     if (bad_index) *bad_index = i;
     return st;
@@ -33,14 +29,6 @@ inline zigz_status shape(size_t n) {
     if (n & (n - 1)) return ZIGZ_ERR_LENGTH_NOT_POWER_OF_TWO;
     if (log2_of(n) > SV_MAX_LOG2_N) return ZIGZ_ERR_INVALID_ARGUMENT;
     return ZIGZ_OK;
-}
-// u64 -> packed u32; false at the first value >= p
-inline bool narrow(const uint64_t *src, size_t n, uint32_t *dst) {
-    for (size_t j = 0; j < n; j++) {
-        if (src[j] >= SV_P) return false;
-        dst[j] = (uint32_t)src[j];
-    }
-    return true;
 }
 
 // What zigz_[dev_]mle_eval_batch says about its arguments before anything runs: ZIGZ_OK, or the status the single entry

@@ -1,5 +1,5 @@
-// Device-side helpers shared by the translation units that build Merkle trees (kernels.hip, merkle_levels.hip,
-// merkle_batch.hip): the workgroup size, digest loads / stores in the kernels' tree form (keccak.hpp), the timed-launch macro,
+// Device-side helpers shared by every kernel translation unit: the workgroup size, digest loads / stores in the kernels' tree
+// form (keccak.hpp), the streaming load, the wave sum and the descriptor search of the batched launches, the timed-launch macro,
 // the completion flags of launches that publish into pinned memory.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -43,6 +43,28 @@ typedef unsigned int zk_v4u __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void nt_store16(uint4 *dst, const uint4 &v) {  // global_store_dwordx4 ... nt
     zk_v4u x = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(x, reinterpret_cast<zk_v4u *>(dst));
+}
+// A table that is read ONCE by a pass says so: a non-temporal 16-byte load (global_load_dwordx4 ... nt; kernels.hip: k_block_sums)
+__device__ __forceinline__ uint4 stream_load(const uint4 *q) {
+    const zk_v4u v = __builtin_nontemporal_load(reinterpret_cast<const zk_v4u *>(q));
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+// the exact u64 sum of a wave's 64 values, in lane 0
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+// Batched launches: the descriptor that owns workgroup `wg` -- the last one whose first workgroup (first_wg) is <= wg
+template <class T>
+__device__ __forceinline__ unsigned find_first_wg(const T *__restrict__ tabs, unsigned nt, unsigned wg) {
+    unsigned lo = 0, hi = nt;
+    while (hi - lo > 1) {
+        const unsigned mid = (lo + hi) >> 1;
+        if (tabs[mid].first_wg <= wg) lo = mid;
+        else hi = mid;
+    }
+    return lo;
 }
 __device__ __forceinline__ Digest load_digest(const uint8_t *tree, size_t node) {
     const ulonglong2 *q = reinterpret_cast<const ulonglong2 *>(tree + node * 32);
