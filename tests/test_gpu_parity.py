@@ -1369,6 +1369,53 @@ def test_commit_batch_equals_single_jobs(ctx, nv):
 
 
 @pytest.mark.gpu
+def test_commit_batch_stats_are_the_sums_of_single_jobs(ctx):
+    """The build statistics of a batched job in arenas are the sums of its proofs' own jobs' (one tally per proof, added over
+    the batch): 2^15 rows (the smallest size with list-built levels), no small-domain hints, two looping traces whose group
+    is kept and a straight-line one whose group is dropped on the device.  cons_probe_distinct is left out: it depends on
+    whether the probe pass ran and on the learnt list capacities."""
+    import programs
+    import zigz_amd
+    nv, steps = 15, 1 << 15
+    progs = [programs.add_xor_loop((steps - 3) // 4), programs.mixed_loop((steps - 8) // 12 - 3),
+             programs.straight_line_program(7, int(0.9 * steps))]
+    masks = {"small_domain_mask": 0, "run_aware_mask": (0x7fffffff << 2) | (3 << 40),
+             "cons_group_mask": 1 | (1 << 1) | (0x7f << 33) | (1 << 42)}
+    additive = ("run_aware_hashed", "run_aware_dense_nodes", "cons_dense_nodes", "cons_hashed", "list_hash_perms",
+                "keccak_permutations", "eval_constant_columns")
+    saved = {k: ctx.get_option(k) for k in masks}
+    bufs = []
+    try:
+        for p_ in progs:
+            bufs.append(_trace_cols(ctx, p_, nv))
+        stride = bufs[0][1]
+        for k, v in masks.items():
+            ctx.set_option(k, v)
+        ctx.set_option("cons_always", 1)
+        single = []
+        for d, _ in bufs:
+            job = zigz_amd.CommitJob(ctx, d_cols=d, ncols=43, nv=nv, col_stride=stride)
+            job.roots()
+            single.append(ctx.stats())
+            job.end()
+        assert [s["cons_columns"] for s in single] == [10, 10, 0], single  # kept, kept, dropped
+        job = zigz_amd.CommitJob(ctx, d_cols_list=[d for d, _ in bufs], ncols=43, nv=nv, col_stride=stride)
+        job.roots()
+        st = ctx.stats()
+        job.end()
+        print({k: (st[k], [s[k] for s in single]) for k in additive + ("cons_columns", "cons_probe_distinct")})
+        for k in additive:
+            assert st[k] == sum(s[k] for s in single), (k, st[k], [s[k] for s in single])
+        assert st["cons_columns"] == 10 and st["run_aware_columns"] == 33, st
+    finally:
+        ctx.set_option("cons_always", 0)
+        for k, v in saved.items():
+            ctx.set_option(k, v)
+        for d, _ in bufs:
+            ctx.dev_free(d)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("ns", [1, 63, 64, 65, 4096, 4097, 70000])
 def test_witness_from_32_byte_records_synthetic(ctx, ns):
     """the 32-byte step record (imm as i32, the memory triple in a side list a step refers to by index --

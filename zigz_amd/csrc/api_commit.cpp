@@ -3,6 +3,8 @@
 #include "api_internal.hpp"
 
 using namespace zk;
+using cp::ListCaps;
+static_assert(cp::MAX_LEVELS == RUN_MAX_LEVELS && cp::SUMMARY_WORDS == JOB_SUMMARY_WORDS, "commit_plan.hpp restates kernels.hpp");
 
 // ------------------------------------------------------------------ Merkle
 // How much room the lists (and the digests stored in list order) of the structure-aware levels get: learnt from what the
@@ -26,30 +28,86 @@ static void caps_for(zigz_ctx *ctx, size_t npad, unsigned rn, unsigned gn) {
     }
 }
 
+// A TreeRef without any storage yet: no column has a slab, is run-aware or member of the group.
+static TreeRef empty_tree_ref(size_t npad) {
+    TreeRef t{};
+    t.npad = npad;
+    memset(t.slab_of_col, -1, sizeof(t.slab_of_col));
+    memset(t.y_of_col, -1, sizeof(t.y_of_col));
+    memset(t.g_j_of_col, -1, sizeof(t.g_j_of_col));
+    return t;
+}
+// nodes per column on the list-built levels 0 .. top
+static uint64_t list_level_nodes(size_t npad) {
+    uint64_t n = 0;
+    for (unsigned l = 0; l <= run_top_level(npad); l++) n += npad >> l;
+    return n;
+}
+// The list-built levels of the R and G columns of a build of `ncols` columns: fills what t says about them (r_caps / g_caps:
+// room per sub-list, nullptr = the worst case) and returns what the sizes of their storage depend on (commit_plan.hpp).
+static cp::Shape tree_ref_lists(TreeRef &t, const ColMap &R, const ColMap &G, size_t ncols, const unsigned *r_caps, const unsigned *g_caps) {
+    const size_t npad = t.npad;
+    cp::Shape s{npad, R.n, G.n, ncols, 0, 0, 0, 0, 0};
+    t.lists = 1;
+    t.top = run_top_level(npad);
+    if (R.n) {
+        t.r_lists = runs_lists(npad, R.n, r_caps);
+        s.units = runs_units(npad, R.n, t.ubase_off);
+        s.r_entries = t.r_lists.entries;
+        s.meta_words = runs_meta_words(npad, R.n);
+        s.stage_bytes = runs_stage_scratch_bytes(npad, R.n);
+        t.ncols = R.n;
+        for (unsigned y = 0; y < R.n; y++) t.y_of_col[R.c[y]] = (signed char)y;
+    }
+    if (G.n) {
+        t.g_lists = cons_lists(npad, g_caps);
+        s.g_entries = t.g_lists.entries;
+        t.g_ncols = G.n;
+        for (unsigned k = 0; k < G.n; k++) t.g_j_of_col[G.c[k]] = (signed char)k;
+    }
+    return s;
+}
+// ... and the pointers into that storage, region r of the plan at base[space of r] + its offset (g_ctr: the build's G counters)
+static void point_at_regions(MerkleBuild &b, TreeRef &t, const cp::Plan &p, uint8_t *const base[cp::N_SPACES], unsigned long long *g_ctr) {
+    auto at = [&](cp::Region r) { return base[p.space[r]] + p.off[r]; };
+    t.upper = at(cp::UPPER);
+    if (b.rcols.n) {
+        b.r_list = (uint32_t *)at(cp::R_LIST);
+        b.r_stage = at(cp::R_STAGE);
+        t.bitmap = (unsigned long long *)at(cp::R_BITMAP);
+        t.prev = (unsigned short *)at(cp::R_PREV);
+        t.woff = (unsigned short *)at(cp::R_WOFF);
+        t.ubase = (uint32_t *)at(cp::R_UBASE);
+        t.r_store = at(cp::R_STORE);
+    }
+    if (b.gcols.n) {
+        b.g_keys = (unsigned long long *)at(cp::G_KEYS);
+        b.g_idx = (uint32_t *)at(cp::G_IDX);
+        b.g_list = (uint32_t *)at(cp::G_LIST);
+        b.g_rep = (uint32_t *)at(cp::G_REP);
+        t.g_rep = b.g_rep;
+        t.g_store = at(cp::G_STORE);
+        b.g_ctr = g_ctr;
+        t.g_dropped = g_ctr + 8;
+    }
+}
+
 // Builds all levels of `ncols` trees, asynchronously on the stream.
-// ref != nullptr (a commit job): the digests of the list-built levels stay in list order (TreeRef: stores), only densely
-//   built columns get node-addressed slabs (taken from WS_TREE); *ref describes where everything is and stays valid while
+// in.job (a commit job's build): the digests of the list-built levels stay in list order (TreeRef: stores), only densely
+//   built columns get node-addressed slabs (taken from WS_TREE); out->tree describes where everything is and stays valid while
 //   the context's WS_RUNMETA / WS_CONSMETA / WS_TREE workspaces are untouched -- until the job ends.
-// ref == nullptr, or option "run_aware_materialize": every digest of every tree is written into node-addressed slabs
-//   (d_slab if given: single trees that outlive the call; else WS_TREE), one per column.
+// !in.job, or in.materialize: every digest of every tree is written into node-addressed slabs (d_slab if given: single trees
+//   that outlive the call; else WS_TREE), one per column.
 zigz_status build_trees(zigz_ctx *ctx, const uint32_t *d_vals, size_t val_stride, size_t n_values, size_t npad,
-                               uint8_t *d_slab, size_t ncols, bool record, TreeRef *ref) {
+                               uint8_t *d_slab, size_t ncols, bool record, const BuildHints &in, BuildResult *out) {
     const unsigned height = log2_floor(npad);
     const size_t stride = tree_nodes(npad);
-    ctx->stats.small_domain_columns = 0;
-    ctx->stats.run_aware_columns = 0;
-    ctx->stats.run_aware_dense_nodes = 0;
-    ctx->stats.cons_columns = 0;
-    ctx->stats.cons_dense_nodes = 0;
-    ctx->stats.cons_probe_distinct = 0;
-    ctx->build_cons_hinted = 0;
-    ctx->build_cons_levels_nodes = 0;
-    ctx->build_cons_sd = 0;
-    ctx->build_top_perms = 0;
+    const bool job = in.job;
+    *out = BuildResult{};
     if (record) ctx->kev_n = 0;
     // the list counters of a commit job's build are read again by its openings (EvalSkip, the "group dropped" word): they are
     // the job's; any other build on the context counts in the auxiliary pair
-    unsigned long long *const r_ctr = ref ? ctx->d_run_count : ctx->d_run_aux, *const g_ctr = ref ? ctx->d_cons_count : ctx->d_cons_aux;
+    unsigned long long *const r_ctr = job ? ctx->d_run_count : ctx->d_run_aux, *const g_ctr = job ? ctx->d_cons_count : ctx->d_cons_aux;
     // timing mode: every launch (or bracketed group of launches) carries its own begin / end timestamps, by class
     KTime kt_store;
     auto stamp = [&](int cls, uint64_t perms) -> const KTime * {
@@ -74,31 +132,31 @@ zigz_status build_trees(zigz_ctx *ctx, const uint32_t *d_vals, size_t val_stride
     // The top kernel (256 nodes per column -> root) takes all columns together.
     ColMap H{}, R{}, D{}, G{}, GS{};
     const bool big = npad >= RUN_MIN_LEAVES && npad <= RUN_MAX_LEAVES && ncols <= 64;
-    const bool sd_ok = ctx->small_domain_mask && npad >= 1024 && ncols <= 64 && val_stride % 2 == 0 && ((uintptr_t)d_vals & 7) == 0;
-    const bool run_ok = ctx->run_aware_mask && big;
+    const bool sd_ok = in.small_domain_mask && npad >= 1024 && ncols <= 64 && val_stride % 2 == 0 && ((uintptr_t)d_vals & 7) == 0;
+    const bool run_ok = in.run_aware_mask && big;
     // (a content-addressing key packs two child list slots into RUN_NODE_BITS bits each, and a slot is sub-list * capacity +
     // position: at npad == 2^26 a nearly full last sub-list reaches 2^26 + 2047 -- the group path stops one size short of that)
-    bool cons_ok = ctx->cons_group_mask && big && npad < RUN_MAX_LEAVES;
+    bool cons_ok = in.cons_group_mask && big && npad < RUN_MAX_LEAVES;
     unsigned gn_hinted = 0;  // (what the context learnt is filed under the hints, not under whether this build tries the group)
-    for (size_t c = 0; cons_ok && c < ncols; c++) gn_hinted += (unsigned)((ctx->cons_group_mask >> c) & 1);
+    for (size_t c = 0; cons_ok && c < ncols; c++) gn_hinted += (unsigned)((in.cons_group_mask >> c) & 1);
     if (run_ok || cons_ok) {
         unsigned rn_hinted = 0;
         for (size_t c = 0; run_ok && c < ncols; c++)
-            rn_hinted += (unsigned)(((ctx->run_aware_mask >> c) & 1) && !(cons_ok && ((ctx->cons_group_mask >> c) & 1)) &&
-                                    !(sd_ok && ((ctx->small_domain_mask >> c) & 1)));
+            rn_hinted += (unsigned)(((in.run_aware_mask >> c) & 1) && !(cons_ok && ((in.cons_group_mask >> c) & 1)) &&
+                                    !(sd_ok && ((in.small_domain_mask >> c) & 1)));
         caps_for(ctx, npad, rn_hinted, gn_hinted);
     }
     // A context whose last two jobs dropped the group (its traces do not loop) stops trying for a while: the group's columns
     // are then H / D from the start -- no table passes that find nothing, and the tuned dense kernels instead of the list
     // kernel's dense branch -- and every 16th job looks again.
-    if (cons_ok && ref && !ctx->cons_always && ctx->caps.npad == npad && ctx->caps.g_skip) {
+    if (cons_ok && job && !ctx->cons_always && ctx->caps.npad == npad && ctx->caps.g_skip) {
         ctx->caps.g_skip--;
         cons_ok = false;
     }
     auto kind = [&](size_t c) -> int {  // 0 D, 1 H, 2 R, 3 G
-        if (cons_ok && ((ctx->cons_group_mask >> c) & 1)) return 3;
-        if (sd_ok && ((ctx->small_domain_mask >> c) & 1)) return 1;
-        if (run_ok && ((ctx->run_aware_mask >> c) & 1)) return 2;
+        if (cons_ok && ((in.cons_group_mask >> c) & 1)) return 3;
+        if (sd_ok && ((in.small_domain_mask >> c) & 1)) return 1;
+        if (run_ok && ((in.run_aware_mask >> c) & 1)) return 2;
         return 0;
     };
     if (sd_ok || run_ok || cons_ok)
@@ -106,19 +164,13 @@ zigz_status build_trees(zigz_ctx *ctx, const uint32_t *d_vals, size_t val_stride
             const int kd = kind(c);
             ColMap &m = kd == 3 ? G : kd == 1 ? H : kd == 2 ? R : D;
             m.c[m.n++] = (uint8_t)c;
-            if (kd == 3 && sd_ok && ((ctx->small_domain_mask >> c) & 1)) GS.c[GS.n++] = (uint8_t)c;
+            if (kd == 3 && sd_ok && ((in.small_domain_mask >> c) & 1)) GS.c[GS.n++] = (uint8_t)c;
         }
     const bool lists = R.n || G.n;
-    const bool whole = ref == nullptr || ctx->run_aware_materialize;  // every digest into node-addressed slabs
+    const bool whole = !job || in.materialize;  // every digest into node-addressed slabs
     const bool virt = !whole;  // copies / non-representatives / table leaves never written
     // ---- where the digests go
-    TreeRef t{};
-    t.npad = npad;
-    for (int c = 0; c < 64; c++) {
-        t.slab_of_col[c] = -1;
-        t.y_of_col[c] = -1;
-        t.g_j_of_col[c] = -1;
-    }
+    TreeRef t = empty_tree_ref(npad);
     size_t nslab = 0;
     if (whole || !lists) {
         nslab = ncols;
@@ -168,14 +220,24 @@ zigz_status build_trees(zigz_ctx *ctx, const uint32_t *d_vals, size_t val_stride
                                 (uint32_t *)sd_todo, ctx->stream, stamp(3, 0), !virt, nullptr, &hs);
         if (virt)
             for (unsigned k = 0; k < H.n; k++) t.virtual_leaves |= 1ull << H.c[k];
-        ctx->stats.small_domain_columns = H.n;
+        out->sd_cols = H.n;
     }
     MerkleBuild b{};
     unsigned top = 0;
     if (lists) {
-        top = run_top_level(npad);
-        t.lists = 1;
-        t.top = top;
+        // what outlives the build (read by the openings): a commit job keeps it in workspaces of its own, which nothing but
+        // the next commit job touches; otherwise it is scratch like the rest (cp::plan_single).  Only a commit job can repeat
+        // a build that ran out of room: anything else gets the worst case.
+        const cp::Shape shape = tree_ref_lists(t, R, G, ncols, job ? ctx->caps.r : nullptr, job ? ctx->caps.g : nullptr);
+        const cp::Plan plan = cp::plan_single(shape, job);
+        static const int slot[cp::N_SPACES] = {WS_RUNS, WS_RUNMETA, WS_CONS, WS_CONSMETA, WS_OUT64};
+        uint8_t *base[cp::N_SPACES] = {};
+        for (int sp = 0; sp < cp::N_SPACES; sp++) {
+            void *w = nullptr;
+            if (plan.total[sp]) CHK(ws_get(ctx, slot[sp], plan.total[sp], &w));
+            base[sp] = (uint8_t *)w;
+        }
+        top = t.top;
         b.vals = d_vals;
         b.val_stride = val_stride;
         b.n_values = n_values;
@@ -183,84 +245,32 @@ zigz_status build_trees(zigz_ctx *ctx, const uint32_t *d_vals, size_t val_stride
         b.rcols = R;
         b.gcols = G;
         b.gcols_sd = GS;
-        uint64_t level_nodes = 0;
-        for (unsigned l = 0; l <= top; l++) level_nodes += npad >> l;
-        // what outlives the build (read by the openings): a commit job keeps it in workspaces of its own, which nothing but
-        // the next commit job touches; otherwise it is scratch like the rest
-        const bool keep = ref != nullptr;
-        const size_t upper_bytes = ncols * 512 * 32;
+        point_at_regions(b, t, plan, base, g_ctr);
         if (R.n) {
-            // (only a commit job can repeat a build that ran out of room: anything else gets the worst case)
-            t.r_lists = runs_lists(npad, R.n, ref ? ctx->caps.r : nullptr);
-            unsigned long long uoff[RUN_MAX_LEVELS] = {0};
-            const size_t units = runs_units(npad, R.n, uoff);
-            for (unsigned l = 0; l < RUN_MAX_LEVELS; l++) t.ubase_off[l] = uoff[l];
-            const size_t list_bytes = (size_t)t.r_lists.entries * 4, stage_bytes = runs_stage_scratch_bytes(npad, R.n);
-            const size_t meta_n = runs_meta_words(npad, R.n);
-            // kept: bitmap | prev | woff | ubase | digests in list order
-            const size_t kept = meta_n * 12 + units * 4 + 64 + (size_t)t.r_lists.entries * 32 + 64;
-            void *w, *mw;
-            CHK(ws_get(ctx, WS_RUNS, ((list_bytes + 63) & ~(size_t)63) + stage_bytes + 64 + (keep ? 0 : kept), &w));
-            b.r_list = (uint32_t *)w;
-            b.r_stage = (uint8_t *)w + ((list_bytes + 63) & ~(size_t)63);
-            if (keep) CHK(ws_get(ctx, WS_RUNMETA, kept + upper_bytes, &mw));
-            else mw = (uint8_t *)w + ((((list_bytes + 63) & ~(size_t)63) + stage_bytes + 64 + 63) & ~(size_t)63);
-            uint8_t *q = (uint8_t *)mw;
-            t.bitmap = (unsigned long long *)q; q += meta_n * 8;
-            t.prev = (unsigned short *)q; q += meta_n * 2;
-            t.woff = (unsigned short *)q; q += meta_n * 2;
-            t.ubase = (uint32_t *)q; q += (units * 4 + 63) & ~(size_t)63;
-            t.r_store = q; q += (size_t)t.r_lists.entries * 32;
-            if (keep) t.upper = (uint8_t *)mw + kept;
-            t.ncols = R.n;
-            for (unsigned y = 0; y < R.n; y++) t.y_of_col[R.c[y]] = (signed char)y;
             b.r_ctr = r_ctr;
-            ctx->stats.run_aware_columns = R.n;
-            ctx->stats.run_aware_dense_nodes = (uint64_t)R.n * level_nodes;
+            out->run_cols = R.n;
+            out->run_dense = (uint64_t)R.n * list_level_nodes(npad);
         }
         if (G.n) {
-            // table (generation-tagged: cleared only when the workspace is new or the generations run out) + list: scratch;
-            // the representative slots and the digests in list order are kept while the trees are read through them
-            t.g_lists = cons_lists(npad, ref ? ctx->caps.g : nullptr);
-            const size_t key_bytes = 2 * npad * 8, idx_bytes = 2 * npad * 4, list_bytes = ((size_t)t.g_lists.entries * 4 + 63) & ~(size_t)63;
-            const size_t kept = 2 * npad * 4 + (size_t)t.g_lists.entries * G.n * 32 + 64;
-            const bool upper_here = keep && !R.n;
-            void *w, *mw;
-            CHK(ws_get(ctx, WS_CONS, key_bytes + idx_bytes + list_bytes + 64 + (keep ? 0 : kept), &w));
-            b.g_keys = (unsigned long long *)w;
-            b.g_idx = (uint32_t *)((uint8_t *)w + key_bytes);
-            b.g_list = (uint32_t *)((uint8_t *)w + key_bytes + idx_bytes);
-            if (keep) CHK(ws_get(ctx, WS_CONSMETA, kept + (upper_here ? upper_bytes : 0), &mw));
-            else mw = (uint8_t *)w + ((key_bytes + idx_bytes + list_bytes + 64 + 63) & ~(size_t)63);
-            b.g_rep = (uint32_t *)mw;
-            t.g_rep = b.g_rep;
-            t.g_store = (uint8_t *)mw + 2 * npad * 4;
-            if (upper_here) t.upper = (uint8_t *)mw + kept;
+            // the table (generation-tagged, at offset 0 of its workspace): cleared only when the workspace is new or the
+            // generations run out
+            void *const w = base[cp::SP_CONS];
             if (ctx->cons_table != w || ctx->cons_table_bytes != ctx->ws_bytes[WS_CONS] || ctx->cons_gen + RUN_MAX_LEVELS + 1 >= 4096) {
-                HIPCHK(ctx, hipMemsetAsync(w, 0, key_bytes, ctx->stream));  // generation 0 = free
+                HIPCHK(ctx, hipMemsetAsync(w, 0, plan.bytes[cp::G_KEYS], ctx->stream));  // generation 0 = free
                 ctx->cons_table = w;
                 ctx->cons_table_bytes = ctx->ws_bytes[WS_CONS];
                 ctx->cons_gen = 1;
             }
             b.g_gen = ctx->cons_gen;
             ctx->cons_gen += top + 1;
-            b.g_ctr = g_ctr;
             b.g_has_slabs = whole || ctx->caps.g_slabs;
             static const bool always_probe = getenv("ZIGZ_CONS_PROBE_ALWAYS") != nullptr;  // (A/B)
-            b.g_no_probe = ref && ctx->caps.npad == npad && ctx->caps.g_kept >= 2 && !ctx->cons_always && !always_probe;
-            t.g_ncols = G.n;
-            t.g_dropped = g_ctr + 8;
-            for (unsigned k = 0; k < G.n; k++) t.g_j_of_col[G.c[k]] = (signed char)k;
+            b.g_no_probe = job && ctx->caps.npad == npad && ctx->caps.g_kept >= 2 && !ctx->cons_always && !always_probe;
             if (virt)
                 for (unsigned k = 0; k < GS.n; k++) t.g_sd_mask |= 1ull << GS.c[k];
-            ctx->build_cons_hinted = G.n;
-            ctx->build_cons_levels_nodes = level_nodes;
-            ctx->build_cons_sd = GS.n;
-        }
-        if (!t.upper) {  // not a job: the top levels are scratch too
-            void *u;
-            CHK(ws_get(ctx, WS_OUT64, upper_bytes, &u));
-            t.upper = (uint8_t *)u;
+            out->cons_hinted = G.n;
+            out->cons_levels_nodes = list_level_nodes(npad);
+            out->cons_sd = GS.n;
         }
         b.t = t;
         if (ctx->debug_skip != 2) launch_structure(b, ctx->stream, ctx->debug_skip == 0, stamp(4, 0));
@@ -271,12 +281,12 @@ zigz_status build_trees(zigz_ctx *ctx, const uint32_t *d_vals, size_t val_stride
                                     &gs);
         }
     }
-    if (ref) *ref = t;
+    out->tree = t;
     unsigned first_top = 0;  // the level the top kernel starts from
     if (lists) {
         for (unsigned l = 0; l <= top; l++) {
             size_t expect = 0;  // what the last build of this shape held here, + 25 % + the sub-lists' slack (sizing only)
-            if (ref && ctx->caps.npad == npad && (ctx->caps.r_last[l] || ctx->caps.g_last[l])) {
+            if (job && ctx->caps.npad == npad && (ctx->caps.r_last[l] || ctx->caps.g_last[l])) {
                 auto more = [](unsigned v) { return (size_t)RUN_SUBS * (v + v / 4 + 8); };
                 expect = (R.n ? more(ctx->caps.r_last[l]) : 0) + (G.n ? more(ctx->caps.g_last[l]) * G.n : 0) +
                          (G.n && ctx->caps.last_dropped ? (size_t)G.n * (npad >> l) : 0);
@@ -315,8 +325,7 @@ zigz_status build_trees(zigz_ctx *ctx, const uint32_t *d_vals, size_t val_stride
         }
     }
     if (height) {
-        ctx->build_top_perms = (uint64_t)ncols * ((npad >> first_top) - 1);
-        if (ctx->debug_skip != 1) launch_merkle_top(t, first_top, height, ncols, ctx->stream, stamp(6, ctx->build_top_perms));
+        if (ctx->debug_skip != 1) launch_merkle_top(t, first_top, height, ncols, ctx->stream, stamp(6, (uint64_t)ncols * ((npad >> first_top) - 1)));
     }
     if (lists && whole) launch_fill_virtual(b, ctx->stream);
     HIPCHK(ctx, hipGetLastError());
@@ -351,6 +360,14 @@ zigz_status keccak_times_collect(zigz_ctx *ctx) {
     ctx->stats.run_aware_us = us[4] + us[5];
     ctx->kev_n = 0;
     return ZIGZ_OK;
+}
+
+// what a build leaves in the context's stats at once (the counters' share follows in zigz_commit_roots)
+static void publish_build_stats(zigz_ctx *ctx, const BuildResult &built) {
+    ctx->stats.small_domain_columns = built.sd_cols;
+    ctx->stats.run_aware_columns = built.run_cols;
+    ctx->stats.run_aware_dense_nodes = built.run_dense;
+    ctx->stats.cons_columns = ctx->stats.cons_dense_nodes = ctx->stats.cons_probe_distinct = 0;
 }
 
 struct zigz_merkle {
@@ -388,7 +405,11 @@ extern "C" zigz_status zigz_merkle_commit(zigz_ctx *ctx, const uint64_t *values,
         HIPCHK(ctx, hipMalloc((void **)&t->d_vals, n * 4));
         HIPCHK(ctx, hipMalloc((void **)&t->d_tree, tree_nodes(npad) * 32));
         CHK(upload_u64(ctx, values, n, t->d_vals, false));
-        CHK(build_trees(ctx, t->d_vals, n, n, npad, t->d_tree, 1));
+        BuildResult built;
+        const zigz_status bs = build_trees(ctx, t->d_vals, n, n, npad, t->d_tree, 1, false,
+                                           BuildHints{ctx->small_domain_mask, ctx->run_aware_mask, ctx->cons_group_mask, ctx->run_aware_materialize, false}, &built);
+        publish_build_stats(ctx, built);
+        CHK(bs);
         void *d_root;  // the root leaves the device through the gather kernel: tree form -> canonical SHA3 bytes
         CHK(ws_get(ctx, WS_MISC, 64, &d_root));
         launch_gather_nodes(t->d_tree, tree_nodes(npad), tree_level_offset(npad, t->height), (uint8_t *)d_root, 1, ctx->stream);
@@ -482,13 +503,13 @@ struct zigz_commit_job {
     // what its build asked for (turned into stats when the counters have arrived; other calls may run in between)
     uint64_t m_small, m_run, m_cons;
     bool m_whole;
-    uint64_t run_cols, run_dense, sd_cols, cons_hinted, cons_levels_nodes, cons_sd, perms0;
+    cp::JobFacts facts;
     // a batched job (zigz_commit_begin_batch): nz proofs of ncols1 columns each; ncols = nz * ncols1.  arena: every proof's
     // build lives in its own zstride bytes of the context's WS_BATCH workspace (TreeRef::zstride); flat (nz > 1, zstride == 0):
     // the proofs' columns were gathered into one table of ncols columns and built densely like any other.
     unsigned nz;
     size_t ncols1, zstride;
-    size_t off_r_ctr, off_g_ctr;  // byte offsets of a proof's list counters in its arena
+    size_t off_r_ctr;  // byte offset of a proof's R list counters in its arena
     bool no_eval_skip;  // built without its structure passes (option debug_skip 2, measurement only): the "column changed" words
                         // were never written, so the eval must not take them for "constant"
 };
@@ -499,46 +520,35 @@ static zigz_status job_build(zigz_commit_job *job) {
     const size_t ncols = job->ncols, nv = job->nv;
     CHK(timed_begin(ctx, 2));
     job->whole = job->m_whole;
-    {   // build with the hints of the job's begin, whatever the context's options say by now
-        const uint64_t s0 = ctx->small_domain_mask, r0 = ctx->run_aware_mask, c0 = ctx->cons_group_mask;
-        const bool w0 = ctx->run_aware_materialize;
-        ctx->small_domain_mask = job->m_small;
-        ctx->run_aware_mask = job->m_run;
-        ctx->cons_group_mask = job->m_cons;
-        ctx->run_aware_materialize = job->m_whole;
-        const zigz_status bs = build_trees(ctx, job->d_cols, job->col_stride, job->N, job->N, nullptr, ncols, ctx->timing, &job->tree);
-        ctx->small_domain_mask = s0;
-        ctx->run_aware_mask = r0;
-        ctx->cons_group_mask = c0;
-        ctx->run_aware_materialize = w0;
-        CHK(bs);
-    }
+    // (the hints of the job's begin, whatever the context's options say by now)
+    BuildResult built;
+    const zigz_status bs = build_trees(ctx, job->d_cols, job->col_stride, job->N, job->N, nullptr, ncols, ctx->timing,
+                                       BuildHints{job->m_small, job->m_run, job->m_cons, job->m_whole, true}, &built);
+    publish_build_stats(ctx, built);
+    CHK(bs);
+    job->tree = built.tree;
     if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
     // roots + the counters of the build -> contiguous device buffer -> pinned staging (async), then the "built" event
     // zero-copy: the summary kernel stores the roots and counters into the pinned host buffer itself (no copy command)
     const DoneFlag done = done_flag(ctx, 0);
     job->roots_seq = done.seq;
     launch_job_summary(job->tree, (unsigned)nv, ctx->h_roots, ncols,
-                       ctx->stats.run_aware_columns ? ctx->d_run_count : nullptr,
-                       (ctx->stats.small_domain_columns || ctx->build_cons_sd) ? ctx->d_sd_fallbacks : nullptr,
-                       ctx->build_cons_hinted ? ctx->d_cons_count : nullptr, ctx->stream, done);
+                       built.run_cols ? ctx->d_run_count : nullptr, (built.sd_cols || built.cons_sd) ? ctx->d_sd_fallbacks : nullptr,
+                       built.cons_hinted ? ctx->d_cons_count : nullptr, ctx->stream, done);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(job->built, ctx->stream));
     // hinted columns take levels 0 and 1 (N + N/2 digests) from the tables (waves that had to hash are counted in
     // small_domain_fallback_waves, read in zigz_commit_roots; they are not added back here)
-    job->run_cols = ctx->stats.run_aware_columns;
-    job->run_dense = ctx->stats.run_aware_dense_nodes;
-    job->sd_cols = ctx->stats.small_domain_columns;
-    job->cons_hinted = ctx->build_cons_hinted;
-    job->cons_levels_nodes = ctx->build_cons_levels_nodes;
-    job->cons_sd = ctx->build_cons_sd;
-    job->perms0 = (uint64_t)ncols * (2 * job->N - 1) - job->sd_cols * (job->N + job->N / 2);
+    job->facts = cp::JobFacts{built.run_cols, built.run_dense, built.sd_cols, built.cons_hinted, built.cons_levels_nodes, built.cons_sd,
+                              (uint64_t)ncols * (2 * job->N - 1) - built.sd_cols * (job->N + job->N / 2), job->N};
     job->no_eval_skip = ctx->debug_skip == 2;
     return ZIGZ_OK;
 }
 
-static zigz_status job_begin(zigz_ctx *ctx, const uint32_t *d_cols, size_t ncols, size_t col_stride, size_t nv,
-                             zigz_commit_job **out) {
+// A new job of nz proofs (0: a single job) of ncols1 columns and 2^nv rows each becomes the context's active job once
+// build(job) has queued its build.
+template <class Build>
+static zigz_status job_new(zigz_ctx *ctx, unsigned nz, size_t ncols1, size_t nv, zigz_commit_job **out, Build build) {
     if (ctx->active_job) {
         set_err(ctx, "a commit job is already active on this context");
         return ZIGZ_ERR_BAD_STATE;
@@ -547,20 +557,16 @@ static zigz_status job_begin(zigz_ctx *ctx, const uint32_t *d_cols, size_t ncols
     if (!job) return ZIGZ_ERR_OUT_OF_MEMORY;
     memset(job, 0, sizeof(*job));
     job->ctx = ctx;
-    job->ncols = ncols;
+    job->nz = nz;
+    job->ncols1 = nz ? ncols1 : 0;
+    job->ncols = ncols1 * (nz ? nz : 1);
     job->nv = nv;
     job->N = (size_t)1 << nv;
-    job->col_stride = col_stride;
-    job->d_cols = d_cols;
-    job->m_small = ctx->small_domain_mask;
-    job->m_run = ctx->run_aware_mask;
-    job->m_cons = ctx->cons_group_mask;
-    job->m_whole = ctx->run_aware_materialize;
     auto body = [&]() -> zigz_status {
         HIPCHK(ctx, hipEventCreateWithFlags(&job->built, hipEventDisableTiming));
-        return job_build(job);
+        return build(job);
     };
-    zigz_status st = body();
+    const zigz_status st = body();
     if (st != ZIGZ_OK) {
         if (job->built) (void)hipEventDestroy(job->built);
         delete job;
@@ -569,6 +575,19 @@ static zigz_status job_begin(zigz_ctx *ctx, const uint32_t *d_cols, size_t ncols
     ctx->active_job = job;
     *out = job;
     return ZIGZ_OK;
+}
+
+static zigz_status job_begin(zigz_ctx *ctx, const uint32_t *d_cols, size_t ncols, size_t col_stride, size_t nv,
+                             zigz_commit_job **out) {
+    return job_new(ctx, 0, ncols, nv, out, [&](zigz_commit_job *job) {
+        job->col_stride = col_stride;
+        job->d_cols = d_cols;
+        job->m_small = ctx->small_domain_mask;
+        job->m_run = ctx->run_aware_mask;
+        job->m_cons = ctx->cons_group_mask;
+        job->m_whole = ctx->run_aware_materialize;
+        return job_build(job);
+    });
 }
 
 // ---- a batched job: several proofs' columns in ONE commit job (zigz_commit_begin_batch)
@@ -593,56 +612,15 @@ static zigz_status job_build_batch_arena(zigz_commit_job *job, const uint32_t *c
         else return ZIGZ_ERR_INVALID_ARGUMENT;  // (a densely built column: not in this form)
     }
     const size_t stride = N;  // column stride inside an arena
-    TreeRef t{};
-    t.npad = npad;
-    for (int c = 0; c < 64; c++) {
-        t.slab_of_col[c] = -1;
-        t.y_of_col[c] = -1;
-        t.g_j_of_col[c] = -1;
-    }
-    t.lists = 1;
-    t.top = run_top_level(npad);
-    // ---- the arena's layout (byte offsets, the same for every proof)
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += align256(bytes); return o; };
-    const size_t o_cols = take(nc * stride * 4);
-    const size_t o_rctr = take(RUN_CTR_WORDS * 8), o_gctr = take(RUN_CTR_WORDS * 8);
-    size_t o_rlist = 0, o_rstage = 0, o_bitmap = 0, o_prev = 0, o_woff = 0, o_ubase = 0, o_rstore = 0;
-    size_t meta_n = 0;
-    if (R.n) {
-        t.r_lists = runs_lists(npad, R.n, nullptr);
-        unsigned long long uoff[RUN_MAX_LEVELS] = {0};
-        const size_t units = runs_units(npad, R.n, uoff);
-        for (unsigned l = 0; l < RUN_MAX_LEVELS; l++) t.ubase_off[l] = uoff[l];
-        meta_n = runs_meta_words(npad, R.n);
-        o_rlist = take((size_t)t.r_lists.entries * 4);
-        o_rstage = take(runs_stage_scratch_bytes(npad, R.n) + 64);
-        o_bitmap = take(meta_n * 8);
-        o_prev = take(meta_n * 2);
-        o_woff = take(meta_n * 2);
-        o_ubase = take(units * 4 + 64);
-        o_rstore = take((size_t)t.r_lists.entries * 32);
-        t.ncols = R.n;
-        for (unsigned y = 0; y < R.n; y++) t.y_of_col[R.c[y]] = (signed char)y;
-    }
-    size_t o_keys = 0, o_idx = 0, o_glist = 0, o_grep = 0, o_gstore = 0, o_slab = 0;
-    const size_t key_bytes = 2 * npad * 8;
-    if (G.n) {
-        t.g_lists = cons_lists(npad, nullptr);
-        o_keys = take(key_bytes);
-        o_idx = take(2 * npad * 4);
-        o_glist = take((size_t)t.g_lists.entries * 4);
-        o_grep = take(2 * npad * 4);
-        o_gstore = take((size_t)t.g_lists.entries * G.n * 32);
-        o_slab = take((size_t)G.n * tree_nodes(npad) * 32);  // where a dropped group's columns are built densely
-        t.g_ncols = G.n;
-        for (unsigned k = 0; k < G.n; k++) {
-            t.g_j_of_col[G.c[k]] = (signed char)k;
-            t.slab_of_col[G.c[k]] = (signed char)k;
-        }
-    }
-    const size_t o_upper = take(nc * 512 * 32);
-    const size_t S = align256(at);
+    TreeRef t = empty_tree_ref(npad);
+    const cp::Shape shape = tree_ref_lists(t, R, G, nc, nullptr, nullptr);
+    for (unsigned k = 0; k < G.n; k++) t.slab_of_col[G.c[k]] = (signed char)k;  // where a dropped group's columns are built densely
+    // ---- the arena's layout (byte offsets, the same for every proof): columns | R counters | G counters | the lists' storage
+    // (cp::plan_arena) | the group's slabs
+    const size_t o_cols = 0, o_rctr = align256(nc * stride * 4), o_gctr = o_rctr + align256(RUN_CTR_WORDS * 8);
+    const cp::Plan plan = cp::plan_arena(shape, o_gctr + align256(RUN_CTR_WORDS * 8));
+    const size_t o_slab = plan.total[0], o_keys = plan.off[cp::G_KEYS], key_bytes = plan.bytes[cp::G_KEYS];
+    const size_t S = o_slab + align256((size_t)G.n * tree_nodes(npad) * 32);
     if ((size_t)nz * S > ((size_t)48 << 30)) return ZIGZ_ERR_OUT_OF_MEMORY;
     void *w;
     const void *w_before = ctx->ws[WS_BATCH];
@@ -662,7 +640,6 @@ static zigz_status job_build_batch_arena(zigz_commit_job *job, const uint32_t *c
         ctx->batch_tab_off = o_keys;
         ctx->batch_gen = 1;
     }
-    t.upper = a0 + o_upper;
     MerkleBuild b{};
     b.vals = (const uint32_t *)(a0 + o_cols);
     b.val_stride = stride;
@@ -670,26 +647,11 @@ static zigz_status job_build_batch_arena(zigz_commit_job *job, const uint32_t *c
     b.npad = npad;
     b.rcols = R;
     b.gcols = G;
-    if (R.n) {
-        t.bitmap = (unsigned long long *)(a0 + o_bitmap);
-        t.prev = (unsigned short *)(a0 + o_prev);
-        t.woff = (unsigned short *)(a0 + o_woff);
-        t.ubase = (uint32_t *)(a0 + o_ubase);
-        t.r_store = a0 + o_rstore;
-        b.r_list = (uint32_t *)(a0 + o_rlist);
-        b.r_stage = a0 + o_rstage;
-        b.r_ctr = (unsigned long long *)(a0 + o_rctr);
-    }
+    uint8_t *const base[cp::N_SPACES] = {a0};
+    point_at_regions(b, t, plan, base, (unsigned long long *)(a0 + o_gctr));
+    if (R.n) b.r_ctr = (unsigned long long *)(a0 + o_rctr);
     if (G.n) {
         t.slab = a0 + o_slab;
-        t.g_rep = (const uint32_t *)(a0 + o_grep);
-        t.g_store = a0 + o_gstore;
-        t.g_dropped = (const unsigned long long *)(a0 + o_gctr) + 8;
-        b.g_keys = (unsigned long long *)(a0 + o_keys);
-        b.g_idx = (uint32_t *)(a0 + o_idx);
-        b.g_list = (uint32_t *)(a0 + o_glist);
-        b.g_rep = (uint32_t *)(a0 + o_grep);
-        b.g_ctr = (unsigned long long *)(a0 + o_gctr);
         b.g_has_slabs = 1;
         b.g_gen = ctx->batch_gen;
         ctx->batch_gen += t.top + 1;
@@ -711,22 +673,14 @@ static zigz_status job_build_batch_arena(zigz_commit_job *job, const uint32_t *c
     job->col_stride = stride;
     job->zstride = S;
     job->off_r_ctr = o_rctr;
-    job->off_g_ctr = o_gctr;
     job->whole = false;
     const DoneFlag done = done_flag(ctx, 0);
     job->roots_seq = done.seq;
     launch_job_summary(t, height, ctx->h_roots, nc, R.n ? b.r_ctr : nullptr, nullptr, G.n ? b.g_ctr : nullptr, ctx->stream, done);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(job->built, ctx->stream));
-    uint64_t level_nodes = 0;
-    for (unsigned l = 0; l <= t.top; l++) level_nodes += npad >> l;
-    job->run_cols = R.n;
-    job->run_dense = (uint64_t)R.n * level_nodes;
-    job->sd_cols = 0;
-    job->cons_hinted = G.n;
-    job->cons_levels_nodes = level_nodes;
-    job->cons_sd = 0;
-    job->perms0 = (uint64_t)nc * (2 * N - 1);
+    const uint64_t level_nodes = list_level_nodes(npad);
+    job->facts = cp::JobFacts{R.n, (uint64_t)R.n * level_nodes, 0, G.n, level_nodes, 0, (uint64_t)nc * (2 * N - 1), N};
     job->no_eval_skip = ctx->debug_skip == 2;
     return ZIGZ_OK;
 }
@@ -739,24 +693,10 @@ extern "C" zigz_status zigz_commit_begin_batch(zigz_ctx *ctx, const uint32_t *co
     for (size_t z = 0; z < nproofs; z++)
         if (!d_cols[z]) return ZIGZ_ERR_INVALID_ARGUMENT;
     if (nproofs == 1) return job_begin(ctx, d_cols[0], ncols, col_stride, nv, out);
-    if (ctx->active_job) {
-        set_err(ctx, "a commit job is already active on this context");
-        return ZIGZ_ERR_BAD_STATE;
-    }
     const size_t N = (size_t)1 << nv;
     const bool arena = N >= RUN_MIN_LEAVES && N <= ((size_t)1 << BATCH_ARENA_MAX_NV) && ncols <= 64 && (ctx->run_aware_mask || ctx->cons_group_mask);
-    if (N >= RUN_MIN_LEAVES && !arena) return ZIGZ_ERR_INVALID_ARGUMENT;  // (large tables: one job per proof)
-    zigz_commit_job *job = new (std::nothrow) zigz_commit_job();
-    if (!job) return ZIGZ_ERR_OUT_OF_MEMORY;
-    memset(job, 0, sizeof(*job));
-    job->ctx = ctx;
-    job->nz = (unsigned)nproofs;
-    job->ncols1 = ncols;
-    job->ncols = ncols * nproofs;
-    job->nv = nv;
-    job->N = N;
-    auto body = [&]() -> zigz_status {
-        HIPCHK(ctx, hipEventCreateWithFlags(&job->built, hipEventDisableTiming));
+    return job_new(ctx, (unsigned)nproofs, ncols, nv, out, [&](zigz_commit_job *job) -> zigz_status {
+        if (N >= RUN_MIN_LEAVES && !arena) return ZIGZ_ERR_INVALID_ARGUMENT;  // (large tables: one job per proof)
         if (arena) {
             job->m_small = 0;
             job->m_run = ctx->run_aware_mask;
@@ -776,16 +716,7 @@ extern "C" zigz_status zigz_commit_begin_batch(zigz_ctx *ctx, const uint32_t *co
         job->m_small = job->m_run = job->m_cons = 0;
         job->m_whole = false;
         return job_build(job);
-    };
-    const zigz_status st = body();
-    if (st != ZIGZ_OK) {
-        if (job->built) (void)hipEventDestroy(job->built);
-        delete job;
-        return st;
-    }
-    ctx->active_job = job;
-    *out = job;
-    return ZIGZ_OK;
+    });
 }
 
 extern "C" zigz_status zigz_commit_begin_dev(zigz_ctx *ctx, const uint32_t *d_cols, size_t ncols, size_t col_stride,
@@ -830,42 +761,15 @@ extern "C" zigz_status zigz_commit_roots(zigz_commit_job *job, uint8_t *roots) {
         // What the lists of the structure-aware levels needed: the context remembers it for its next builds, and a build that
         // ran out of room (or found its group dropped with nowhere to build the columns densely) is repeated here with more.
         // This is the one place where a proof may pay for a second build: the first time a context meets a new kind of trace.
-        const unsigned long long flags = h_cnt[6];
-        const bool r_over = (flags & 1) != 0, g_over = ((flags >> 8) & 1) != 0, g_noslab = ((flags >> 8) & 2) != 0;
-        const bool dropped = h_cnt[4] != 0;
-        ListCaps &c = ctx->caps;
         bool again = false;
         if (job->zstride) {  // a batched job's lists have their worst-case room: nothing to learn, nothing can have run out
             for (unsigned z = 0; z < job->nz; z++)
-                if (h_cnt[(size_t)z * JOB_SUMMARY_WORDS + 6]) {
+                if (h_cnt[(size_t)z * JOB_SUMMARY_WORDS + cp::SUM_FLAGS]) {
                     set_err(ctx, "batched commit job: a list ran out of its worst-case room (proof %u)", z);
                     return ZIGZ_ERR_BAD_STATE;
                 }
-        } else if (job->tree.lists && c.npad == job->N) {
-            for (unsigned l = 0; l <= job->tree.top; l++) {
-                const unsigned long long ru = h_cnt[8 + l], gu = h_cnt[8 + RUN_MAX_LEVELS + l];
-                c.r_last[l] = job->run_cols ? (unsigned)(ru ? ru : 1) : 0;
-                c.g_last[l] = job->cons_hinted && !dropped ? (unsigned)(gu ? gu : 1) : 0;
-                if (job->run_cols && (r_over ? ru > c.r[l] : ru * 10 > (unsigned long long)c.r[l] * 8))
-                    c.r[l] = (unsigned)(ru + ru / 4 + 64);
-                if (job->cons_hinted && !dropped && (g_over ? gu > c.g[l] : gu * 10 > (unsigned long long)c.g[l] * 8))
-                    c.g[l] = (unsigned)(gu + gu / 4 + 64);
-                // A G list that ran out of room hides what the levels above it need: the nodes that found no slot share their
-                // sub-list's last one, so their parents' keys look alike and the level above counts too few.  Learning one level
-                // per build would take more builds than a job may repeat: give every level at least the room of the one below
-                // (the lists never get more than "every node hashed", cons_lists).
-                if (g_over && job->cons_hinted && !dropped && l > 0 && c.g[l] < c.g[l - 1]) c.g[l] = c.g[l - 1];
-            }
-            c.last_dropped = dropped;
-            if (dropped) c.g_slabs = true;  // this context's traces do not repeat: give the group's columns slabs from now on
-            if (job->cons_hinted) {
-                c.g_drops = dropped ? c.g_drops + 1 : 0;
-                c.g_kept = dropped ? 0 : c.g_kept + 1;
-                // ... and after the second drop in a row, skip the attempt for 15 jobs -- twice as many after every further attempt
-                // that is dropped again (a context shared by a service's lanes sees hundreds of jobs of one kind of trace)
-                if (c.g_drops >= 2) c.g_skip = 15u << (c.g_drops - 2 < 6 ? c.g_drops - 2 : 6);
-            }
-            again = r_over || (g_over && !dropped) || g_noslab;
+        } else if (job->tree.lists) {
+            again = cp::learn_caps(ctx->caps, h_cnt, job->facts);
         }
         if (!again) break;
         if (attempt >= 3) {
@@ -876,67 +780,9 @@ extern "C" zigz_status zigz_commit_roots(zigz_commit_job *job, uint8_t *roots) {
         CHK(job_build(job));
     }
     memcpy(roots, ctx->h_roots, job->ncols * 32);
-    if (job->zstride) {  // a batched job: the sums over its proofs
-        const uint64_t nz = job->nz;
-        uint64_t r_hashed = 0, g_hashed = 0, g_kept = 0, g_distinct = 0, constant = 0, dense_g = 0;
-        for (unsigned z = 0; z < job->nz; z++) {
-            const unsigned long long *h = h_cnt + (size_t)z * JOB_SUMMARY_WORDS;
-            r_hashed += job->run_cols ? h[0] : 0;
-            constant += job->run_cols ? h[7] : 0;
-            if (job->cons_hinted) {
-                g_distinct += h[5];
-                if (!h[4]) { g_kept++; g_hashed += h[3]; }
-                else dense_g += job->cons_hinted * job->cons_levels_nodes;  // dropped: its columns were hashed densely
-            }
-        }
-        ctx->stats.run_aware_columns = job->run_cols;
-        ctx->stats.run_aware_dense_nodes = job->run_dense * nz;
-        ctx->stats.run_aware_hashed = r_hashed;
-        ctx->stats.small_domain_columns = 0;
-        ctx->stats.small_domain_fallback_waves = 0;
-        ctx->stats.cons_columns = g_kept ? job->cons_hinted : 0;
-        ctx->stats.cons_dense_nodes = job->cons_hinted * job->cons_levels_nodes * g_kept;
-        ctx->stats.cons_hashed = g_hashed;
-        ctx->stats.cons_probe_distinct = g_distinct;
-        ctx->stats.list_hash_perms = r_hashed + g_hashed + dense_g;
-        ctx->stats.keccak_permutations = job->perms0 * nz - (job->run_dense * nz - r_hashed) - (ctx->stats.cons_dense_nodes - g_hashed);
-        job->const_cols = constant;
-        ctx->stats.eval_constant_columns = constant;
-        job->state = 1;
-        return ZIGZ_OK;
-    }
-    // the run-aware levels hashed h_cnt[0] of their run_dense nodes
-    const uint64_t N = job->N;
-    ctx->stats.run_aware_columns = job->run_cols;
-    ctx->stats.run_aware_dense_nodes = job->run_dense;
-    ctx->stats.small_domain_columns = job->sd_cols;
-    ctx->stats.keccak_permutations = job->perms0;
-    ctx->stats.run_aware_hashed = job->run_cols ? h_cnt[0] : 0;
-    job->const_cols = job->run_cols ? h_cnt[7] : 0;
-    ctx->stats.eval_constant_columns = job->const_cols;
-    ctx->stats.keccak_permutations -= ctx->stats.run_aware_dense_nodes - ctx->stats.run_aware_hashed;
-    ctx->stats.small_domain_fallback_waves = job->sd_cols ? h_cnt[1] : 0;
-    ctx->stats.list_hash_perms = ctx->stats.run_aware_hashed;
-    // the group: kept (digests computed for its cons_dense_nodes nodes: h_cnt[3]) or dropped on the device (its small-domain
-    // members then took levels 0 and 1 from the tables, everything else was hashed densely)
-    ctx->stats.cons_columns = ctx->stats.cons_dense_nodes = ctx->stats.cons_hashed = 0;
-    ctx->stats.cons_probe_distinct = 0;
-    if (job->cons_hinted) {
-        ctx->stats.cons_probe_distinct = h_cnt[5];
-        if (!h_cnt[4]) {
-            ctx->stats.cons_columns = job->cons_hinted;
-            ctx->stats.cons_dense_nodes = job->cons_hinted * job->cons_levels_nodes;
-            ctx->stats.cons_hashed = h_cnt[3];
-            ctx->stats.keccak_permutations -= ctx->stats.cons_dense_nodes - ctx->stats.cons_hashed;
-            ctx->stats.list_hash_perms += ctx->stats.cons_hashed;
-        } else {
-            ctx->stats.small_domain_columns += job->cons_sd;
-            ctx->stats.keccak_permutations -= job->cons_sd * (N + N / 2);
-            ctx->stats.small_domain_fallback_waves += h_cnt[2];
-            ctx->stats.list_hash_perms += job->cons_hinted * job->cons_levels_nodes - job->cons_sd * (N + N / 2);
-        }
-    }
-    if (ctx->timing) {
+    // the stats: the sums over the job's proofs (a flat batch is ONE build of all its columns)
+    job->const_cols = cp::job_stats(ctx->stats, h_cnt, job->zstride ? job->nz : 1, job->facts);
+    if (ctx->timing && !job->zstride) {
         float ms = 0;
         HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
         ctx->stats.merkle_build_us = (double)ms * 1000.0;
@@ -972,32 +818,26 @@ extern "C" zigz_status zigz_commit_open_all(zigz_commit_job *job, const uint64_t
             indices[c] = h_idx[c];
         }
         // columns the run-aware structure pass of THIS job found constant are not read again (EvalSkip, kernels.hpp): of the 43
-        // witness columns of a program that uses a handful of registers, most
+        // witness columns of a program that uses a handful of registers, most.  A batched job in arenas: column c = column
+        // c % ncols1 of proof c / ncols1, always in the radix form.
+        const bool arena = job->zstride != 0;
+        const bool use = job->facts.run_cols && !job->no_eval_skip && (arena || (job->tree.lists && job->col_stride >= job->N));
         EvalSkip skip;
-        if (job->zstride) {  // a batched job in arenas: column c = column c % ncols1 of proof c / ncols1 (kernels.hpp: EvalSkip)
+        if (arena) {
             skip.ncols1 = (unsigned)job->ncols1;
             skip.z_in = job->zstride / 4;
             skip.z_changed = job->zstride / 8;
-            memcpy(skip.y_of_col, job->tree.y_of_col, sizeof(skip.y_of_col));
-            if (job->run_cols && !job->no_eval_skip) {
-                skip.changed = (const unsigned long long *)((const uint8_t *)ctx->ws[WS_BATCH] + job->off_r_ctr) + RUN_CHANGED;
-                ctx->stats.eval_constant_columns = job->const_cols;
-            } else {
-                ctx->stats.eval_constant_columns = 0;
-            }
-            CHK(timed_begin(ctx, 4));
-            CHK(dev_eval_radix(ctx, job->d_cols, job->col_stride, ncols, nv, points, z_val, &skip));
-            CHK(timed_end(ctx, 4, &ctx->stats.eval_us));
-        } else {
-            if (job->tree.lists && job->run_cols && job->col_stride >= job->N && !job->no_eval_skip) {
-                skip.changed = ctx->d_run_count + RUN_CHANGED;  // (the job's own counters: no other build on the context adds to them)
-                ctx->stats.eval_constant_columns = job->const_cols;  // (what dev_eval_radix sizes its launch by: this job's count)
-                memcpy(skip.y_of_col, job->tree.y_of_col, sizeof(skip.y_of_col));
-            }
-            CHK(timed_begin(ctx, 4));
-            CHK(dev_eval_folds(ctx, job->d_cols, job->col_stride, ncols, nv, points, z_val, skip.changed ? &skip : nullptr));
-            CHK(timed_end(ctx, 4, &ctx->stats.eval_us));
         }
+        if (arena || use) memcpy(skip.y_of_col, job->tree.y_of_col, sizeof(skip.y_of_col));
+        // (the job's own counters: no other build on the context adds to them)
+        const unsigned long long *r_ctr = arena ? (const unsigned long long *)((const uint8_t *)ctx->ws[WS_BATCH] + job->off_r_ctr) : ctx->d_run_count;
+        if (use) skip.changed = r_ctr + RUN_CHANGED;
+        const size_t n_const = use ? job->const_cols : 0;
+        if (arena || use) ctx->stats.eval_constant_columns = n_const;
+        CHK(timed_begin(ctx, 4));
+        if (arena) CHK(dev_eval_radix(ctx, job->d_cols, job->col_stride, ncols, nv, points, z_val, &skip, n_const));
+        else CHK(dev_eval_folds(ctx, job->d_cols, job->col_stride, ncols, nv, points, z_val, use ? &skip : nullptr, n_const));
+        CHK(timed_end(ctx, 4, &ctx->stats.eval_us));
         const DoneFlag done = done_flag(ctx, 1);
         launch_paths(job->tree, job->tree.npad, (unsigned)nv, job->d_cols, job->col_stride, h_idx, z_sib, z_dirs, z_leaf,
                      job->zstride ? job->ncols1 : ncols, ctx->stream, done);

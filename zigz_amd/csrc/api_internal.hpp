@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "batch_host.hpp"
+#include "commit_plan.hpp"
 #include "field.hpp"
 #include "host_hash.hpp"
 #include "host_parallel.hpp"
@@ -29,16 +30,6 @@ using namespace zk;
 enum { WS_IN64 = 0, WS_IN32, WS_OUT32, WS_OUT64, WS_SCRATCH, WS_TREE, WS_FOLD, WS_MISC, WS_COLS, WS_LASSO, WS_DEDUP, WS_WITNESS, WS_RUNS, WS_RUNMETA, WS_CONS, WS_CONSMETA, WS_BATCH, WS_SCBATCH, WS_SCBATCH_IN, WS_VERIFY, WS_OPEN, WS_MLEBATCH, WS_MLEBATCH_PART, WS_MLEBATCH_IN, WS_SLOTS };
 
 constexpr int KEV_MAX = 72;
-struct ListCaps {
-    size_t npad;
-    unsigned rn, gn;
-    unsigned r[RUN_MAX_LEVELS], g[RUN_MAX_LEVELS];  // entries per sub-list and level
-    bool g_slabs;  // this context's traces made the group be dropped: give its columns slabs up front
-    unsigned g_drops, g_skip;  // consecutive builds that dropped the group; builds left that do not even try it
-    unsigned g_kept;           // consecutive builds that kept it (from the second on the probe pass is left out)
-    unsigned r_last[RUN_MAX_LEVELS], g_last[RUN_MAX_LEVELS];  // the longest sub-list of the LAST build per level (0: none yet): launch sizing only
-    bool last_dropped;  // ... and whether it dropped its group (whose columns are then hashed densely by the level launches)
-};
 struct zigz_ctx {
     int device;
     hipStream_t own_stream;
@@ -93,9 +84,7 @@ struct zigz_ctx {
     void *cons_table;
     size_t cons_table_bytes;
     unsigned cons_gen;
-    // what the last build asked for; turned into stats when its counters have arrived (zigz_commit_roots)
-    uint64_t build_cons_hinted, build_cons_levels_nodes, build_cons_sd, build_top_perms;
-    ListCaps caps;  // room for the lists of the structure-aware levels, learnt from earlier builds (caps_for)
+    cp::ListCaps caps;  // room for the lists of the structure-aware levels, learnt from earlier builds (caps_for)
     size_t batch_tab_S, batch_tab_off;  // the content-addressing tables of the batched jobs' arenas (WS_BATCH) as last cleared
     unsigned batch_tab_nz, batch_gen;
     unsigned batch_reserve;  // option: proofs to size the batched jobs' workspaces for (a service's largest batch), so that they
@@ -182,16 +171,28 @@ zigz_status bind_launch(zigz_ctx *ctx, const uint32_t *d_in, size_t in_stride, u
 void bind_pool_reset(zigz_ctx *ctx);
 zigz_status bind_pool_collect(zigz_ctx *ctx);
 zigz_status dev_eval_radix(zigz_ctx *ctx, const uint32_t *d_cols, size_t col_stride, size_t ncols, size_t nv,
-                                  const uint64_t *points, uint32_t *d_vals, const EvalSkip *skip = nullptr);
+                                  const uint64_t *points, uint32_t *d_vals, const EvalSkip *skip = nullptr, size_t n_const = 0);
+// skip, n_const: the columns the eval may leave out and how many of them there are (sizes the launch)
 zigz_status dev_eval_folds(zigz_ctx *ctx, const uint32_t *d_cols, size_t col_stride, size_t ncols, size_t nv,
-                                  const uint64_t *points /*host, ncols*nv*/, uint32_t *d_vals, const EvalSkip *skip = nullptr);
+                                  const uint64_t *points /*host, ncols*nv*/, uint32_t *d_vals, const EvalSkip *skip = nullptr, size_t n_const = 0);
 zigz_status sumcheck_core(zigz_ctx *ctx, const uint32_t *d_in, size_t n, uint32_t *d_scratch,
                                  const uint64_t *fixed, uint64_t *rounds, uint64_t *point, uint64_t *final_eval);
 zigz_status stage_in(zigz_ctx *ctx, const uint64_t *in, size_t n, uint32_t **d_out);
 zigz_status lasso_mapping_check(const uint64_t *table, size_t table_rows, const uint64_t *queries, size_t n_queries, size_t w,
                                 const uint64_t *mapping, size_t n_mapping);
+// what a build is asked for: the column hints (bit c = column c), whether every digest goes into node-addressed slabs, and
+// whether it is a commit job's build (the job's counters, learnt list room, digests kept in list order for its openings)
+struct BuildHints {
+    uint64_t small_domain_mask, run_aware_mask, cons_group_mask;
+    bool materialize, job;
+};
+// ... and what it did: where the digests are and the figures zigz_commit_roots turns into stats once the counters have arrived
+struct BuildResult {
+    TreeRef tree;
+    uint64_t run_cols, run_dense, sd_cols, cons_hinted, cons_levels_nodes, cons_sd;
+};
 zigz_status build_trees(zigz_ctx *ctx, const uint32_t *d_vals, size_t val_stride, size_t n_values, size_t npad,
-                               uint8_t *d_slab, size_t ncols, bool record = false, TreeRef *ref = nullptr);
+                               uint8_t *d_slab, size_t ncols, bool record, const BuildHints &in, BuildResult *out);
 zigz_status keccak_times_collect(zigz_ctx *ctx);
 size_t mle_batch_fill(const uint32_t *const *d_tables, const size_t *ns, size_t k, const uint64_t *points, bool reversed,
                       MleBatchTab *tab, uint32_t *f);

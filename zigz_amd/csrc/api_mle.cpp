@@ -150,13 +150,13 @@ extern "C" zigz_status zigz_dev_mle_bind_sums(zigz_ctx *ctx, const uint32_t *d_i
 // leaving 1024 elements per column that a weighted dot product with the eq weights of point[9..0] finishes.
 // HBM traffic 4*N B per column instead of 12*N for v successive binds.  Exact arithmetic => same value.
 zigz_status dev_eval_radix(zigz_ctx *ctx, const uint32_t *d_cols, size_t col_stride, size_t ncols, size_t nv,
-                                  const uint64_t *points, uint32_t *d_vals, const EvalSkip *skip) {
+                                  const uint64_t *points, uint32_t *d_vals, const EvalSkip *skip, size_t n_const) {
     const size_t N = (size_t)1 << nv;
     const unsigned k2 = 10, k1 = (unsigned)nv - k2;
     const size_t m = (size_t)1 << k2, nb = (size_t)1 << k1;
     // a thread folds rloops x 16 rows: fewer when most columns are skipped, so that the launch still fills the chip (13 of 43
     // columns x 16 groups are 208 workgroups on 256 CUs)
-    const size_t active = skip ? ncols - (size_t)ctx->stats.eval_constant_columns : ncols;
+    const size_t active = skip ? ncols - n_const : ncols;
     const int rloops = active * 2 <= ncols && nb % 16 == 0 ? (active * 4 <= ncols + 3 ? 1 : 2) : 4;
     const size_t groups = radix_fold_groups(nb, rloops);
     if (nv * ncols * 4 > PIN_WORDS * 8 / 2) return ZIGZ_ERR_INVALID_ARGUMENT;
@@ -185,7 +185,7 @@ zigz_status dev_eval_radix(zigz_ctx *ctx, const uint32_t *d_cols, size_t col_str
         ctx->pool_used = 1;
         ctx->pool_is_fold = ctx->active_job != nullptr;
         // one read of the tables (those of the columns that are not skipped) + the partial sums
-        ctx->pool_bytes = (uint64_t)(ncols - (skip ? ctx->stats.eval_constant_columns : 0)) * (N * 4 + groups * m * 8);
+        ctx->pool_bytes = (uint64_t)(ncols - (skip ? n_const : 0)) * (N * 4 + groups * m * 8);
     }
     // (finalize and dot stay two launches: fused into one workgroup per column they took 60-69 us in a batch against 13 + 9 --
     // a column's 64 groups summed by ONE workgroup instead of four)
@@ -199,7 +199,7 @@ zigz_status dev_eval_radix(zigz_ctx *ctx, const uint32_t *d_cols, size_t col_str
 // point reversed (exact arithmetic => the same canonical value as the reference's O(v*2^v) loop).
 // Batched over `ncols` columns, column c using point row c.  Result words land in d_vals[ncols].
 zigz_status dev_eval_folds(zigz_ctx *ctx, const uint32_t *d_cols, size_t col_stride, size_t ncols, size_t nv,
-                                  const uint64_t *points /*host, ncols*nv*/, uint32_t *d_vals, const EvalSkip *skip) {
+                                  const uint64_t *points /*host, ncols*nv*/, uint32_t *d_vals, const EvalSkip *skip, size_t n_const) {
     const size_t N = (size_t)1 << nv;
     if (nv == 0) {
         launch_gather_first(d_cols, col_stride, d_vals, ncols, ctx->stream);
@@ -207,7 +207,7 @@ zigz_status dev_eval_folds(zigz_ctx *ctx, const uint32_t *d_cols, size_t col_str
         return ZIGZ_OK;
     }
     if (nv >= 14 && nv <= 24 && col_stride % 4 == 0 && aligned16(d_cols) && !ctx->fold_eval)
-        return dev_eval_radix(ctx, d_cols, col_stride, ncols, nv, points, d_vals, skip);
+        return dev_eval_radix(ctx, d_cols, col_stride, ncols, nv, points, d_vals, skip, n_const);
     // r table in Montgomery form, [round][col], staged in the upper half of the pinned buffer so the
     // asynchronous H2D copy never reads freed host memory
     if (nv * ncols * 4 > PIN_WORDS * 8 / 2) return ZIGZ_ERR_INVALID_ARGUMENT;

@@ -405,6 +405,7 @@ void launch_gather_nodes(const uint8_t *d_tree, size_t tree_stride_nodes, size_t
 //   tables), [3] d_g_ctr[0] (digests computed on the content-addressed levels), [4] d_g_ctr[8] (group dropped?), [5] d_g_ctr[9]
 //   (its distinct leaves), [6] d_r_ctr[10] | d_g_ctr[10] << 8 (out of room / slabs missing), [7] constant R columns, then per level l < RUN_MAX_LEVELS
 //   the longest sub-list of the R lists [8 + l] and of the G lists [8 + RUN_MAX_LEVELS + l]; null pointers read as 0
+//   (the host reads them by name: commit_plan.hpp, cp::SummaryWord)
 constexpr unsigned JOB_SUMMARY_WORDS = 8 + 2 * RUN_MAX_LEVELS;
 // the counters a build's kernels add to (2 words of small-domain fall-backs, RUN_CTR_WORDS words each of the R and G lists; null =
 // not used by this build), zeroed by one launch
