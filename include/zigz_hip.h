@@ -591,6 +591,43 @@ zigz_status zigz_sumcheck_verify_batch(zigz_ctx *ctx, const uint64_t *const *tab
                                        uint64_t *expected_evals, uint64_t *oracle_evals, size_t *n_rejected,
                                        size_t *bad_index);
 
+/* k independent sumchecks of a PRODUCT of multilinear tables in shared launches: instance i proves
+ *   sum_{x in {0,1}^v_i} prod_{j < d_i} f_{i,j}(x),   d_i = degrees[i] in 1..ZIGZ_PRODUCT_MAX_DEGREE,
+ * every factor of ns[i] = 2^v_i elements; d_factors holds sum d_i pointers, instance by instance.  This is SumcheckProver.prove
+ * (src/proofs/sumcheck_prover.zig:26-91) with the round polynomial generalised: with a_j = f_j[x], b_j = f_j[x + m/2] (x < m/2)
+ * the round's g(t) = sum_x prod_j (a_j + t (b_j - a_j)) in coefficient form c_0..c_d (the degree-2 and degree-3 round polynomials
+ * the reference's proof format reserves, src/prover/proof.zig:61-77; the verifier is sumcheck_verifier.zig:172-205 with d + 1
+ * coefficients).  The bind is partialEval's, MSB-first (multilinear.zig:166-173); every instance has a fresh transcript and per
+ * round absorbs c_0..c_d in order, then draws the challenge (sumcheck_protocol.zig:176-184).  fixed_challenges != NULL is the
+ * proveInteractive form: sum v_i challenges, concatenated in instance order, and no transcript.
+ * Outputs, concatenated in instance order: claimed_sums[k] (the sum itself), rounds ((d_i + 1) v_i canonical words per
+ * instance), points (v_i), factor_evals (d_i: each factor fully bound, i.e. its extension at the reversed point) and
+ * final_evals[k] (their product).  For d_i = 1 rounds, points and final_evals are byte for byte what
+ * zigz_dev_sumcheck_prove_batch writes for the same table.  There is no single-instance entry: k = 1 is the single.
+ * Schedule: one data pass per round over every instance still longer than 1024 (at most one small copy and two launches per
+ * round, whatever k is); the shorter tables finish on the host after one hand-off.  The caller's tables are only read: the same
+ * table may serve as several factors of one instance (f * f) and in several instances.
+ * Every argument is checked for every instance before anything is launched or written; the first failing instance's index goes
+ * to *bad_index (if non-NULL): ZIGZ_ERR_INVALID_ARGUMENT for ctx or an array NULL, k > ZIGZ_BATCH_MAX, a degree outside
+ * 1..ZIGZ_PRODUCT_MAX_DEGREE, a factor that is NULL or not 16-byte aligned, ns[i] > 2^ZIGZ_PRODUCT_MAX_LOG2_N (the exact u64
+ * sums); ZIGZ_ERR_NO_VARIABLES for ns[i] == 1; ZIGZ_ERR_LENGTH_NOT_POWER_OF_TWO; ZIGZ_ERR_NOT_CANONICAL for a fixed challenge
+ * >= p.  The instances longer than 1024 must together make fewer than 2^24 chunks of 8192 elements, one launch's grid
+ * (ZIGZ_ERR_INVALID_ARGUMENT otherwise, before anything is launched).  k == 0 returns ZIGZ_OK and touches nothing.  Leaves the hint options, zigz_kernel_stats, an active commit job and open
+ * zigz_merkle_batch handles alone; queues on the context's stream. */
+#define ZIGZ_PRODUCT_MAX_DEGREE 3
+#define ZIGZ_PRODUCT_MAX_LOG2_N 30
+zigz_status zigz_dev_sumcheck_prove_product_batch(zigz_ctx *ctx, size_t k, const unsigned *degrees,
+                                                  const uint32_t *const *d_factors, const size_t *ns,
+                                                  const uint64_t *fixed_challenges, uint64_t *claimed_sums, uint64_t *rounds,
+                                                  uint64_t *points, uint64_t *factor_evals, uint64_t *final_evals,
+                                                  size_t *bad_index);
+/* host tables (canonical u64, ZIGZ_ERR_NOT_CANONICAL with the instance's index otherwise), narrowed and uploaded in one copy */
+zigz_status zigz_sumcheck_prove_product_batch(zigz_ctx *ctx, size_t k, const unsigned *degrees,
+                                              const uint64_t *const *factors, const size_t *ns,
+                                              const uint64_t *fixed_challenges, uint64_t *claimed_sums, uint64_t *rounds,
+                                              uint64_t *points, uint64_t *factor_evals, uint64_t *final_evals,
+                                              size_t *bad_index);
+
 /* ---------------------------------------------------------------- host SHA3 sponge / transcript
  * FiatShamirTranscript   src/core/hash.zig:255-324 (sequential by construction: stays on the host) */
 zigz_transcript *zigz_transcript_new(void);

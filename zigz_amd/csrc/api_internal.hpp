@@ -27,7 +27,7 @@
 using namespace zk;
 
 // ------------------------------------------------------------------ context
-enum { WS_IN64 = 0, WS_IN32, WS_OUT32, WS_OUT64, WS_SCRATCH, WS_TREE, WS_FOLD, WS_MISC, WS_COLS, WS_LASSO, WS_DEDUP, WS_WITNESS, WS_RUNS, WS_RUNMETA, WS_CONS, WS_CONSMETA, WS_BATCH, WS_SCBATCH, WS_SCBATCH_IN, WS_VERIFY, WS_OPEN, WS_MLEBATCH, WS_MLEBATCH_PART, WS_MLEBATCH_IN, WS_SLOTS };
+enum { WS_IN64 = 0, WS_IN32, WS_OUT32, WS_OUT64, WS_SCRATCH, WS_TREE, WS_FOLD, WS_MISC, WS_COLS, WS_LASSO, WS_DEDUP, WS_WITNESS, WS_RUNS, WS_RUNMETA, WS_CONS, WS_CONSMETA, WS_BATCH, WS_SCBATCH, WS_SCBATCH_IN, WS_VERIFY, WS_OPEN, WS_MLEBATCH, WS_MLEBATCH_PART, WS_MLEBATCH_IN, WS_PRODUCT, WS_PRODUCT_WORK, WS_PRODUCT_IN, WS_SLOTS };
 
 constexpr int KEV_MAX = 72;
 struct zigz_ctx {

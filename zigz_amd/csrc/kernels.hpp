@@ -569,4 +569,34 @@ void launch_mle_batch_eval(const MleBatchTab *d_tabs, unsigned nt, unsigned nwg,
 void launch_mle_batch_finish(const MleBatchTab *d_tabs, unsigned nt, const unsigned long long *d_part, uint64_t *out, hipStream_t s,
                              DoneFlag done);
 
+// ---- batched product sumcheck (sumcheck_product.hip): the round polynomials of sum_x prod_{j<d} f_j(x), d <= 3, for k
+// independent instances, one data pass per round.  A workgroup owns one chunk of PRODUCT_CHUNK consecutive elements of one
+// instance's current tables (a smaller table is one partial chunk); product_host.hpp holds the host side.
+constexpr unsigned PRODUCT_CHUNK = 8192;
+constexpr unsigned PRODUCT_MAX_DEGREE = 3;    // ZIGZ_PRODUCT_MAX_DEGREE
+constexpr unsigned PRODUCT_MAX_LOG2_N = 30;   // ZIGZ_PRODUCT_MAX_LOG2_N: a coefficient's exact u64 sum cannot wrap
+constexpr unsigned PRODUCT_SUMS = PRODUCT_MAX_DEGREE + 1;  // sums per workgroup / result words per instance (d + 1 used)
+struct ProductTab {  // one instance in one pass; its workgroups are [first_wg, first_wg of instance j + 1)
+    const uint32_t *in[PRODUCT_MAX_DEGREE];  // the d factor tables the pass reads: m packed canonical values each, 16-byte aligned
+    uint32_t *out[PRODUCT_MAX_DEGREE];       // bind pass: the bound tables (m / 2 values); out[j] == in[j] binds in place
+    uint64_t m;                              // current length, a power of two (> 1024 in the sums and bind passes)
+    uint64_t tail_off;                       // tails pass: first word of the instance's d tables in the published u32 array
+    uint32_t d;
+    uint32_t r_m;                            // bind pass: the challenge the tables are bound with, Montgomery form
+    uint32_t first_wg;
+    uint32_t slot;                           // the instance's PRODUCT_SUMS result words start at out + PRODUCT_SUMS * slot
+};
+inline size_t product_wgs(size_t m) { return (m + PRODUCT_CHUNK - 1) / PRODUCT_CHUNK; }
+// round 0: part[PRODUCT_SUMS wg + c] = the workgroup's exact sum of the coefficient-c terms of its index pairs (i, i + m / 2)
+void launch_product_sums(const ProductTab *d_tabs, unsigned nt, unsigned nwg, unsigned long long *d_part, hipStream_t s);
+// a later round: binds every table with r_m (out[q] = bind(in[q], in[q + m/2])) and sums the coefficient terms of the BOUND
+// tables' index pairs (q, q + m/4) in the same pass
+void launch_product_bind(const ProductTab *d_tabs, unsigned nt, unsigned nwg, unsigned long long *d_part, hipStream_t s);
+// one workgroup per instance: its workgroups' partials added, reduced mod p once, into out[PRODUCT_SUMS slot + c] (pinned host
+// memory), completion signalled under `done`
+void launch_product_finish(const ProductTab *d_tabs, unsigned nt, const unsigned long long *d_part, uint64_t *out, hipStream_t s,
+                           DoneFlag done);
+// one workgroup per instance: its d tables (m <= 1024 values each) into pinned memory as u32, table j at tail_off + j m
+void launch_product_tails(const ProductTab *d_tabs, unsigned nt, uint32_t *h_dst, hipStream_t s, DoneFlag done);
+
 }  // namespace zk

@@ -469,6 +469,45 @@ class Context:
         ptrs = (vp * max(len(ns), 1))(*[int(d) for d in d_tables])
         return self._sumcheck_verify_batch(lib.zigz_dev_sumcheck_verify_batch, ptrs, ns, claimed_sums, proofs, flags)
 
+    # ---- batched product sumcheck prover (k independent sums of products of 1..3 tables per call, one data pass per round)
+    def _product_batch(self, fn, ptrs, degrees, ns, challenges):
+        k = len(ns)
+        nvs = [max(int(n).bit_length() - 1, 0) for n in ns]
+        nf = max(sum(degrees), 1)
+        dg = (C.c_uint * max(k, 1))(*[int(d) for d in degrees])
+        nsa = (C.c_size_t * max(k, 1))(*[int(n) for n in ns])
+        cs, csp = _out_u64(k)
+        r, rp = _out_u64(sum((d + 1) * v for d, v in zip(degrees, nvs)))
+        pt, ptp = _out_u64(sum(nvs))
+        fv, fvp = _out_u64(nf)
+        fe, fep = _out_u64(k)
+        cp = None
+        if challenges is not None:
+            c, cp = self._cat_u64(challenges)
+        bad = C.c_size_t(0)
+        self.check_batch(fn(self.h, k, dg, ptrs, nsa, cp, csp, rp, ptp, fvp, fep, C.byref(bad)), bad)
+        out, ro, vo, fo = [], 0, 0, 0
+        for i, (d, v) in enumerate(zip(degrees, nvs)):
+            out.append((int(cs[i]), r[ro: ro + (d + 1) * v].copy(), pt[vo: vo + v].copy(), fv[fo: fo + d].copy(), int(fe[i])))
+            ro, vo, fo = ro + (d + 1) * v, vo + v, fo + d
+        return out
+
+    def sumcheck_prove_product_batch(self, instances, challenges=None):
+        """zigz_sumcheck_prove_product_batch: instances[i] is the list of 1..3 equally long tables whose product is summed;
+        challenges[i] (optional) fixes instance i's challenges (the interactive form, no transcript).  Returns per instance
+        (claimed_sum, rounds [(d + 1) words c_0..c_d per round], point, factor_evals [d], final_eval)."""
+        arrs = [_u64(t) for inst in instances for t in inst]
+        ptrs = (u64p * max(len(arrs), 1))(*[p for _, p in arrs])
+        return self._product_batch(lib.zigz_sumcheck_prove_product_batch, ptrs, [len(inst) for inst in instances],
+                                   [len(inst[0]) if len(inst) else 0 for inst in instances], challenges)
+
+    def dev_sumcheck_prove_product_batch(self, d_instances, ns, challenges=None):
+        """zigz_dev_sumcheck_prove_product_batch: d_instances[i] is the list of instance i's 1..3 device tables (packed u32
+        canonical, 16-byte aligned, ns[i] values each; read only -- the same pointer may repeat)."""
+        flat = [int(d) for inst in d_instances for d in inst]
+        ptrs = (vp * max(len(flat), 1))(*flat)
+        return self._product_batch(lib.zigz_dev_sumcheck_prove_product_batch, ptrs, [len(inst) for inst in d_instances], ns, challenges)
+
     def _merkle_batch_out(self, rc, bad, k, roots, heights, handle, ns, keep):
         self.check_batch(rc, bad)
         res = [(roots[32 * i: 32 * (i + 1)].tobytes(), int(heights[i])) for i in range(k)]
