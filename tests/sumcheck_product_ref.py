@@ -6,10 +6,59 @@ bind (multilinear.zig:166-173), a fresh transcript that absorbs c_0..c_d and the
 u64 arithmetic, reduced after every multiply (operands below p < 2^31: a product is below 2^62), so everything is exact."""
 import numpy as np
 
+import exact_ref
 import oracle_lib as O
 
 P = O.P_BB
 _P = np.uint64(P)
+
+# ---------------------------------------------------------------- inputs where the fused bind pass can go wrong
+# exact_ref.PATTERNS plus two steps (exact_ref's tuple is iterated by the radix tests, so the new names live here)
+STEPS = ("step_up", "step_down")
+# constructed: no product of the other inputs reaches monty_reduce's equality (high word == subtracted word) except as 0 == 0.
+# Here every 16-byte vector of index pairs holds a0 a1 = 1, p - 1, 1, p - 1: a lane's deferred low-word sum is a non-zero multiple
+# of p (found by reasoning, not by search: 1 + (p - 1) = p), which monty_reduce must take to 0, not to p.
+REDUCE_EDGE = ("one_pm1", "all_one")
+PATTERN_SETS = (("all_pm1",) * 3, ("last_pm1",) * 3, ("step_down",) * 3, ("step_up",) * 3, ("alternating", "ramp", "random"),
+                ("last_pm1", "all_pm1", "ramp"), ("step_down", "random", "step_up"))
+EDGE_CHALLENGES = exact_ref.CHALLENGES + ("zero_pm1",)
+
+
+def pattern(name, nv, seed=0):
+    """exact_ref.pattern, and step_up (low half 0, high half p - 1) / step_down (low half p - 1, high half 0) / REDUCE_EDGE's two"""
+    if name == "all_one":
+        return np.ones(1 << nv, dtype=np.uint64)
+    if name == "one_pm1":  # 1, p - 1, 1, p - 1, ...
+        a = np.ones(1 << nv, dtype=np.uint64)
+        a[1::2] = P - 1
+        return a
+    if name not in STEPS:
+        return exact_ref.pattern(name, nv, seed)
+    a = np.zeros(1 << nv, dtype=np.uint64)
+    if name == "step_up":
+        a[len(a) // 2:] = P - 1
+    else:
+        a[:len(a) // 2] = P - 1
+    return a
+
+
+def edge_challenges(name, nv):
+    """exact_ref.challenges, and zero_pm1: 0, p - 1, 0, ... (None for Fiat-Shamir)"""
+    if name != "zero_pm1":
+        return exact_ref.challenges(name, nv)
+    c = np.zeros(nv, dtype=np.uint64)
+    c[1::2] = P - 1
+    return c
+
+
+def edge_cases(nv):
+    """every (pattern names, challenge name) of the edge matrix at 2^nv: PATTERN_SETS x d = 1..3 (the first d patterns of the
+    set) x EDGE_CHALLENGES -- 126 cases over 8 distinct tables (at d = 1 two sets' first patterns repeat: 114 are distinct)"""
+    return [(ps[:d], c) for ps in PATTERN_SETS for d in (1, 2, 3) for c in EDGE_CHALLENGES]
+
+
+def edge_pattern_names():
+    return sorted({n for ps in PATTERN_SETS for n in ps} | set(REDUCE_EDGE))
 
 
 def round_coefficients(fs):
@@ -79,8 +128,15 @@ def claim_chain(claimed, rounds, v, d):
     return True, claim, point
 
 
-def check_proof(tables, proof, fiat_shamir=True):
-    """asserts what a verifier with oracle access to the factors checks of an honest proof"""
+exact_mle_eval = exact_ref.eval  # as check_proof's mle_eval: vectorised, for tables beyond the C oracle's O(v 2^v) eval
+
+
+def check_proof(tables, proof, fiat_shamir=True, mle_eval=None):
+    """asserts what a verifier with oracle access to the factors checks of an honest proof; mle_eval(table, point) evaluates a
+    factor's multilinear extension (the C oracle's by default)"""
+    if mle_eval is None:
+        def mle_eval(f, pt):
+            return O.mle_eval(P, f, pt)
     claimed, rounds, point, evals, fe = proof
     d, v = len(tables), len(point)
     pt = [int(x) for x in point]
@@ -96,7 +152,7 @@ def check_proof(tables, proof, fiat_shamir=True):
     assert expected == int(fe)  # g_v(r_v) == final_eval
     prod = 1
     for f, e in zip(tables, evals):
-        assert int(e) == O.mle_eval(P, f, pt[::-1])  # the prover binds MSB-first: the factor's extension at the reversed point
+        assert int(e) == mle_eval(f, pt[::-1])  # the prover binds MSB-first: the factor's extension at the reversed point
         prod = prod * int(e) % P
     assert prod == int(fe)
 
