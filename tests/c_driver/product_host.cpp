@@ -1,9 +1,9 @@
-// Stand-alone driver of zigz_amd/csrc/product_host.hpp (no GPU, no HIP): built with -fsanitize=address,undefined by
-// tests/test_sumcheck_product_cpu.py and run as a child process.
+// Stand-alone driver of zigz_amd/csrc/product_host.hpp and the rounds of sumcheck_host.hpp under it (no GPU, no HIP): built with
+// -fsanitize=address,undefined by tests/test_sumcheck_product_cpu.py and run as a child process.
 //   prove FILE   FILE holds one instance per line: d n fixed, then d * n table values, then (fixed != 0) log2 n challenges.  Runs
 //                the argument checker over the whole batch (must pass), then proves every instance twice and prints one line per
 //                proof -- claimed_sum final_eval, the (d + 1) v round coefficients, the v challenges, the d factor evaluations:
-//                  first with the host's own rounds (Prover::tail_rounds, what the library runs once a table is <= 1024 long),
+//                  first with the host's own rounds (tail_rounds, what the library runs once a table is <= 1024 long),
 //                  then with every round's coefficients assembled (coefficients()) from sums formed the way the kernels form
 //                  them: raw 64-bit products added as low and high halves, reduced twice per 16 index pairs, i.e. carrying R^-d.
 //   check        runs the argument checkers on bad shapes and prints "case status bad_index written" per case (bad_index -1:
@@ -38,7 +38,7 @@ bool read_instances(const char *path, std::vector<Instance> &out) {
     unsigned long long d, n, fixed, x;
     bool ok = true;
     while (ok && fscanf(fp, "%llu %llu %llu", &d, &n, &fixed) == 3) {
-        if (d < 1 || d > pd::MAX_DEGREE || n < 2 || n > pd::TAIL_MAX || (n & (n - 1))) { ok = false; break; }
+        if (d < 1 || d > pd::MAX_DEGREE || n < 2 || n > HOST_TAIL_MAX || (n & (n - 1))) { ok = false; break; }
         Instance I;
         I.d = (unsigned)d;
         I.n = (size_t)n;
@@ -47,7 +47,7 @@ bool read_instances(const char *path, std::vector<Instance> &out) {
                 ok = fscanf(fp, "%llu", &x) == 1;
                 I.f[j].push_back(x);
             }
-        for (size_t r = 0; fixed && ok && r < pd::log2_of(I.n); r++) {
+        for (size_t r = 0; fixed && ok && r < log2_floor(I.n); r++) {
             ok = fscanf(fp, "%llu", &x) == 1;
             I.fixed.push_back(x);
         }
@@ -70,13 +70,13 @@ void print_proof(const Proof &p) {
     printf("\n");
 }
 
-pd::Prover make_prover(const Instance &I, Proof &p) {
-    const size_t v = pd::log2_of(I.n);
+SumcheckRounds make_prover(const Instance &I, Proof &p) {
+    const size_t v = log2_floor(I.n);
     p.rounds.assign((I.d + 1) * v, SENTINEL);
     p.point.assign(v, SENTINEL);
     p.evals.assign(I.d, SENTINEL);
-    pd::Prover pr;
-    pr.d = I.d;
+    SumcheckRounds pr;
+    pr.ncoef = I.d + 1;
     pr.nv = v;
     pr.claimed_sum = &p.claimed;
     pr.rounds = p.rounds.data();
@@ -124,7 +124,7 @@ void kernel_sums(unsigned d, const std::vector<uint64_t> *f, size_t m, uint64_t 
         }
         for (unsigned c = 0; c <= d; c++) total[c] += d == 1 ? lo[c] : (uint64_t)monty_reduce(hi[c] + monty_reduce(lo[c]));
     }
-    for (unsigned c = 0; c <= d; c++) sums[c] = total[c] % pd::PD_P;
+    for (unsigned c = 0; c <= d; c++) sums[c] = total[c] % ZIGZ_BABYBEAR_P;
 }
 
 int prove(const char *path) {
@@ -151,7 +151,7 @@ int prove(const char *path) {
     for (const Instance &I : inst) {
         {  // the host's own rounds
             Proof p;
-            pd::Prover pr = make_prover(I, p);
+            SumcheckRounds pr = make_prover(I, p);
             std::vector<uint64_t> f[pd::MAX_DEGREE];
             for (unsigned j = 0; j < I.d; j++) f[j] = I.f[j];
             p.fe = pr.tail_rounds(f, p.evals.data());
@@ -160,14 +160,14 @@ int prove(const char *path) {
         }
         {  // every round from kernel-style sums
             Proof p;
-            pd::Prover pr = make_prover(I, p);
+            SumcheckRounds pr = make_prover(I, p);
             std::vector<uint64_t> f[pd::MAX_DEGREE];
             for (unsigned j = 0; j < I.d; j++) f[j] = I.f[j];
             for (size_t m = I.n; m > 1; m /= 2) {
                 uint64_t sums[pd::MAX_DEGREE + 1], c[pd::MAX_DEGREE + 1];
                 kernel_sums(I.d, f, m, sums);
                 pd::coefficients(I.d, sums, c);
-                const uint32_t r_m = to_mont((uint32_t)pr.challenge(c));
+                const uint32_t r_m = to_mont((uint32_t)pr.step(c));
                 for (unsigned j = 0; j < I.d; j++) {
                     for (size_t x = 0; x < m / 2; x++) f[j][x] = bind1((uint32_t)f[j][x], (uint32_t)f[j][x + m / 2], r_m);
                     f[j].resize(m / 2);
@@ -176,7 +176,7 @@ int prove(const char *path) {
             p.fe = 1;
             for (unsigned j = 0; j < I.d; j++) {
                 p.evals[j] = f[j][0];
-                p.fe = pd::f_mul(p.fe, f[j][0]);
+                p.fe = f_mul(p.fe, f[j][0]);
             }
             print_proof(p);
         }
@@ -198,7 +198,7 @@ struct Batch {  // three instances: d = 2 of 8 values, d = 3 of 4, d = 1 of 16
     size_t k = 3;
     Batch() {
         for (auto &t : tab)
-            for (size_t i = 0; i < 16; i++) t[i] = (1234567 * (i + 1) + (size_t)(&t - tab)) % pd::PD_P;
+            for (size_t i = 0; i < 16; i++) t[i] = (1234567 * (i + 1) + (size_t)(&t - tab)) % ZIGZ_BABYBEAR_P;
         for (auto &t : tab) factors.push_back(t);
         fixed.assign(3 + 2 + 4, 5);
         for (auto *a : {claimed, finals}) std::fill(a, a + 3, SENTINEL);
@@ -244,22 +244,22 @@ void run_case(const char *name, Batch &b, bool dev) {
     if (st == ZIGZ_OK && !dev && b.k) {
         size_t fo = 0, vo = 0, ro = 0;
         for (size_t i = 0; i < b.k; i++) {
-            pd::Prover pr;
-            pr.d = deg[i];
-            pr.nv = pd::log2_of(ns[i]);
+            SumcheckRounds pr;
+            pr.ncoef = deg[i] + 1;
+            pr.nv = log2_floor(ns[i]);
             pr.claimed_sum = b.claimed + i;
             pr.rounds = b.rounds + ro;
             pr.point = b.points + vo;
             pr.fixed = b.fixed_p ? b.fixed_p + vo : nullptr;
             std::vector<uint64_t> f[pd::MAX_DEGREE];
-            for (unsigned j = 0; j < pr.d; j++) {
+            for (unsigned j = 0; j < deg[i]; j++) {
                 const uint64_t *t = (const uint64_t *)b.factors[fo + j];
                 f[j].assign(t, t + ns[i]);
             }
             b.finals[i] = pr.tail_rounds(f, b.evals + fo);
-            fo += pr.d;
+            fo += deg[i];
             vo += pr.nv;
-            ro += (pr.d + 1) * pr.nv;
+            ro += pr.ncoef * pr.nv;
         }
     }
     printf("%s_%s %d %lld %d\n", name, dev ? "dev" : "host", (int)st, (long long)bad, b.written() ? 1 : 0);
@@ -280,8 +280,8 @@ int check() {
         { Batch b; b.ns[1] = 3; run_case("n3_1", b, dev); }
         { Batch b; b.ns[2] = 12; run_case("n12_2", b, dev); }
         { Batch b; b.ns[2] = (size_t)1 << 31; run_case("n2p31_2", b, dev); }
-        { Batch b; b.fixed[4] = pd::PD_P; b.fixed_p = b.fixed.data(); run_case("challenge_1", b, dev); }
-        { Batch b; b.fixed[8] = pd::PD_P - 1; b.fixed_p = b.fixed.data(); run_case("challenge_p_minus_1", b, dev); }
+        { Batch b; b.fixed[4] = ZIGZ_BABYBEAR_P; b.fixed_p = b.fixed.data(); run_case("challenge_1", b, dev); }
+        { Batch b; b.fixed[8] = ZIGZ_BABYBEAR_P - 1; b.fixed_p = b.fixed.data(); run_case("challenge_p_minus_1", b, dev); }
         { Batch b; b.a_degrees = nullptr; run_case("no_degrees", b, dev); }
         { Batch b; b.a_ns = nullptr; run_case("no_ns", b, dev); }
         { Batch b; b.a_claimed = nullptr; run_case("no_claimed", b, dev); }
@@ -293,10 +293,10 @@ int check() {
     // device pointers: alignment (never read)
     { Batch b; b.factors[3] = (const uint8_t *)b.tab[3] + 8; run_case("misaligned_1", b, true); }
     // host tables: a value >= p, alone and in front of an instance that fails another check (the calls in order stop at it)
-    { Batch b; b.tab[4][3] = pd::PD_P; run_case("value_1", b, false); }
-    { Batch b; b.tab[1][7] = pd::PD_P; b.ns[2] = 12; run_case("value_0_before_n12_2", b, false); }
-    { Batch b; b.tab[5][0] = pd::PD_P; b.ns[1] = 3; run_case("n3_1_before_value_2", b, false); }
-    { Batch b; b.tab[0][15] = pd::PD_P; run_case("value_past_the_table", b, false); }
+    { Batch b; b.tab[4][3] = ZIGZ_BABYBEAR_P; run_case("value_1", b, false); }
+    { Batch b; b.tab[1][7] = ZIGZ_BABYBEAR_P; b.ns[2] = 12; run_case("value_0_before_n12_2", b, false); }
+    { Batch b; b.tab[5][0] = ZIGZ_BABYBEAR_P; b.ns[1] = 3; run_case("n3_1_before_value_2", b, false); }
+    { Batch b; b.tab[0][15] = ZIGZ_BABYBEAR_P; run_case("value_past_the_table", b, false); }
     return 0;
 }
 

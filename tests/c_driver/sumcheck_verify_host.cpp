@@ -102,7 +102,7 @@ struct Batch {
         for (size_t n : {2, 8, 4, 16}) {
             ns.push_back(n);
             tables.emplace_back(n, 5);
-            for (size_t j = 0; j < sv::log2_of(n); j++) {
+            for (size_t j = 0; j < log2_floor(n); j++) {
                 points.push_back(7 + j);
                 rounds.push_back(11 + j);
                 rounds.push_back(13 + j);
@@ -118,7 +118,7 @@ struct Batch {
     }
     size_t off(size_t i) const {
         size_t o = 0;
-        for (size_t j = 0; j < i; j++) o += sv::log2_of(ns[j]);
+        for (size_t j = 0; j < i; j++) o += log2_floor(ns[j]);
         return o;
     }
 };
@@ -140,7 +140,7 @@ void verify_case(const char *name, const Batch &b, size_t k, bool dev, uint32_t 
 }
 
 int check() {
-    const uint64_t p = sv::SV_P;
+    const uint64_t p = ZIGZ_BABYBEAR_P;
     const Batch good;
     const size_t k = good.ns.size();
     for (int dev = 0; dev < 2; dev++) {

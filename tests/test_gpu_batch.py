@@ -183,6 +183,27 @@ def test_batch_single_commit_batch_on_one_context(ctx):
     assert [_bytes(*x) for x in first] == exp and [_bytes(*x) for x in second] == exp
 
 
+def test_single_batch_and_degree_one_product_give_one_proof(ctx):
+    """the three provers share one host round step and one tail: tail only (2), the 1024 hand-over boundary, the first live size
+    (2048) and one size with a bind round before the hand-over (4096) give byte-identical proofs from each of them"""
+    ns = [2, 1024, 2048, 4096]
+    tables = [O.splitmix64_field(88000 + i, n) for i, n in enumerate(ns)]
+    d = DevTables(ctx, tables)
+    try:
+        single = [ctx.dev_sumcheck_prove(p, n) for p, n in zip(d.ptrs, ns)]
+        batch = ctx.dev_sumcheck_prove_batch(d.ptrs, ns)
+        product = ctx.dev_sumcheck_prove_product_batch([[p] for p in d.ptrs], ns)
+    finally:
+        d.free()
+    for i, t in enumerate(tables):
+        claimed, rounds, point, evals, fe = product[i]
+        exp = _bytes(*single[i])
+        assert exp == _bytes(*O.sumcheck_prove(P, t)), ns[i]
+        assert _bytes(*batch[i]) == exp, ns[i]
+        assert _bytes(rounds, point, fe) == exp and int(evals[0]) == fe, ns[i]
+        assert claimed == (int(rounds[0]) + (int(rounds[0]) + int(rounds[1])) % P) % P == O.mle_sum(P, t), ns[i]
+
+
 def _lasso_case(seed, bits, nq, w, mapping):
     rng = np.random.default_rng(seed)
     n_in, n_out = w

@@ -148,12 +148,6 @@ zigz_status pinned(zigz_ctx *ctx, size_t bytes, uint8_t **out) {
     return ZIGZ_OK;
 }
 
-// a batched entry's failure at entry i: i into *bad_index (when asked for), the status returned
-zigz_status fail_at(size_t *bad_index, size_t i, zigz_status st) {
-    if (bad_index) *bad_index = i;
-    return st;
-}
-
 extern "C" zigz_status zigz_device_set_blocking_sync(int device, int on) {
     int n = 0;
     if (zigz_device_count(&n) != ZIGZ_OK || device < 0 || device >= n) return ZIGZ_ERR_NO_DEVICE;
@@ -412,9 +406,25 @@ zigz_status upload_u64(zigz_ctx *ctx, const uint64_t *h_in, size_t n, uint32_t *
     HIPCHK(ctx, hipMemcpyAsync(hflag, ctx->d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (*hflag) {
-        set_err(ctx, "input contains a value >= p (not a canonical BabyBear element)");
+        set_err(ctx, "%s", NOT_CANONICAL_TEXT);
         return ZIGZ_ERR_NOT_CANONICAL;
     }
+    return ZIGZ_OK;
+}
+
+zigz_status stage_host_tables(zigz_ctx *ctx, const uint64_t *const *tables, const size_t *ns, size_t count,
+                              const std::vector<size_t> &at, uint32_t *h, int slot, const size_t *owner,
+                              std::vector<const uint32_t *> &d, size_t *bad_index) {
+    for (size_t f = 0; f < count; f++)
+        if (!narrow(tables[f], ns[f], h + at[f])) {
+            set_err(ctx, "%s", NOT_CANONICAL_TEXT);
+            return fail_at(bad_index, owner ? owner[f] : f, ZIGZ_ERR_NOT_CANONICAL);
+        }
+    void *d32;
+    CHK(ws_get(ctx, slot, at[count] * 4, &d32));
+    HIPCHK(ctx, hipMemcpyAsync(d32, h, at[count] * 4, hipMemcpyHostToDevice, ctx->stream));
+    d.resize(count);
+    for (size_t f = 0; f < count; f++) d[f] = (const uint32_t *)d32 + at[f];
     return ZIGZ_OK;
 }
 
@@ -624,12 +634,6 @@ extern "C" zigz_status zigz_dev_download_u64(zigz_ctx *ctx, const uint32_t *d_in
     ZIGZ_ENTER(ctx);
     if (!ctx || (n && (!h_out || !d_in))) return ZIGZ_ERR_INVALID_ARGUMENT;
     return download_u64(ctx, d_in, n, h_out);
-}
-
-zigz_status mle_check(size_t n) {  // Multilinear.init, multilinear.zig:36-44
-    if (n == 0) return ZIGZ_ERR_EMPTY_EVALUATIONS;
-    if (!is_pow2(n)) return ZIGZ_ERR_LENGTH_NOT_POWER_OF_TWO;
-    return ZIGZ_OK;
 }
 
 uint32_t host_to_mont(uint64_t canonical) { return (uint32_t)((canonical << 32) % (uint64_t)P); }

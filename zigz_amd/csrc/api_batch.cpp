@@ -1,13 +1,12 @@
 // C ABI of libzigz_hip.so, part 5: the batched provers -- k independent sumchecks (and Lasso proofs) in shared launches.
 //
-// Schedule (DESIGN.md "Batched provers"): every table keeps the single-table radix schedule (radix_host.hpp, shared with
-// radix_run in api_mle.cpp) -- a table of n > HOST_TAIL_MAX elements runs a block-sums pass with k = min(log n - 8, 10), then
+// Schedule (DESIGN.md "Batched provers"): every table keeps the single-table radix schedule (sumcheck_host.hpp: radix_run_batch
+// next to radix_run) -- a table of n > HOST_TAIL_MAX elements runs a block-sums pass with k = min(log n - 8, 10), then
 // folds until m <= 1024; a smaller one goes straight to the tail -- but each GPU pass serves EVERY table still in play in one
 // launch (sumcheck_batch.hip), and between passes the host runs each table's k rounds on its own block sums with its own
 // transcript (RadixProver).  Tables that finish early drop out of later passes; all remaining tables are read back in one
 // hand-off.  Exact arithmetic throughout, so every table's rounds, point and final_eval are those of a call of its own.
 #include "api_internal.hpp"
-#include "radix_host.hpp"
 
 #include <algorithm>
 #include <array>
@@ -20,12 +19,6 @@ void flat_commit_batch(const uint32_t *const *ev, const size_t *n, size_t count,
 
 namespace {
 
-struct BatchOps {  // the three passes of zigz_sumcheck_radix_run_batch
-    void *user;
-    zigz_radix_batch_sums_fn block_sums;
-    zigz_radix_batch_fold_fn fold;
-    zigz_radix_batch_tail_fn read_tail;
-};
 // one instance of zigz_lasso_prove_batch (entry i of its arrays) and where its results go
 struct LassoInst {
     const uint64_t *table;
@@ -38,99 +31,6 @@ struct LassoInst {
 struct LassoOut {
     uint64_t *rounds, *point;
 };
-
-zigz_status first_error(const std::vector<RadixProver> &t) {
-    for (const auto &s : t)
-        if (s.st != ZIGZ_OK) return s.st;
-    return ZIGZ_OK;
-}
-
-// The batched orchestration (the batched radix_run).  ns[i] are powers of two >= 2 (checked by the callers).
-zigz_status radix_run_batch(zigz_ctx *ctx, const BatchOps &ops, size_t k, const size_t *ns, const uint64_t *fixed,
-                            uint64_t *rounds, uint64_t *points, uint64_t *final_evals) {
-    ZIGZ_NOTHROW_BEGIN
-    std::vector<RadixProver> t(k);
-    size_t off = 0;
-    for (size_t i = 0; i < k; i++) {
-        t[i].len = ns[i];
-        t[i].nv = log2_floor(ns[i]);
-        t[i].rounds = rounds + 2 * off;
-        t[i].point = points + off;
-        t[i].fixed = fixed ? fixed + off : nullptr;
-        off += t[i].nv;
-    }
-    std::vector<size_t> live, idx2;
-    std::vector<unsigned> ks, knext;
-    std::vector<uint64_t> sums, weights;
-    for (size_t i = 0; i < k; i++)
-        if ((t[i].k = radix_stage_k(ns[i]))) {
-            live.push_back(i);
-            ks.push_back(t[i].k);
-        }
-    if (!live.empty()) {
-        size_t words = 0;
-        for (size_t i : live) words += (size_t)1 << t[i].k;
-        sums.assign(words, 0);
-        CHK(ops.block_sums(ops.user, live.size(), live.data(), ks.data(), sums.data()));
-        size_t o = 0;
-        for (size_t i : live) {
-            t[i].B.assign(sums.begin() + o, sums.begin() + o + ((size_t)1 << t[i].k));
-            o += (size_t)1 << t[i].k;
-        }
-    }
-    while (!live.empty()) {
-        parallel_for(live.size(), [&](size_t j) { t[live[j]].stage_rounds(); });
-        CHK(first_error(t));
-        size_t wn = 0, sn = 0;
-        ks.clear();
-        knext.clear();
-        for (size_t i : live) {
-            const size_t m = t[i].len >> t[i].k;
-            const unsigned kn = radix_stage_k(m);
-            ks.push_back(t[i].k);
-            knext.push_back(kn);
-            wn += t[i].W.size();
-            sn += kn ? (size_t)1 << kn : 0;
-        }
-        weights.resize(wn);
-        size_t o = 0;
-        for (size_t i : live) {
-            memcpy(weights.data() + o, t[i].W.data(), t[i].W.size() * 8);
-            o += t[i].W.size();
-        }
-        sums.assign(sn, 0);
-        CHK(ops.fold(ops.user, live.size(), live.data(), ks.data(), weights.data(), knext.data(), sn ? sums.data() : nullptr));
-        idx2.clear();
-        o = 0;
-        for (size_t j = 0; j < live.size(); j++) {
-            RadixProver &s = t[live[j]];
-            s.len >>= s.k;
-            if (!knext[j]) continue;
-            s.k = knext[j];
-            s.B.assign(sums.begin() + o, sums.begin() + o + ((size_t)1 << s.k));
-            o += (size_t)1 << s.k;
-            idx2.push_back(live[j]);
-        }
-        live.swap(idx2);
-    }
-    // every remaining table in one hand-off
-    std::vector<size_t> all(k), ms(k), toff(k + 1, 0);
-    for (size_t i = 0; i < k; i++) {
-        all[i] = i;
-        ms[i] = t[i].len;
-        toff[i + 1] = toff[i] + ms[i];
-    }
-    std::vector<uint64_t> tails(toff[k]);
-    CHK(ops.read_tail(ops.user, k, all.data(), ms.data(), tails.data()));
-    for (size_t i = 0; i < toff[k]; i++)
-        if (tails[i] >= P) return ZIGZ_ERR_NOT_CANONICAL;
-    parallel_for(k, [&](size_t i) {
-        std::vector<uint64_t> tail(tails.begin() + toff[i], tails.begin() + toff[i + 1]);
-        final_evals[i] = t[i].tail_rounds(tail);
-    });
-    return first_error(t);
-    ZIGZ_NOTHROW_END(ctx)
-}
 
 // ------------------------------------------------------------------ the passes on the GPU
 // Workspaces (sized from the batch's first pass, which is its largest, and kept by the context; no allocation inside the loop):
@@ -345,23 +245,14 @@ zigz_status dev_batch_run(zigz_ctx *ctx, const uint32_t *const *d_tables, const 
     GpuBatch g;
     CHK(gpu_batch_init(ctx, g, k, d_tables, ns));
     const BatchOps ops{&g, gpu_batch_block_sums, gpu_batch_fold, gpu_batch_read_tail};
-    return radix_run_batch(ctx, ops, k, ns, fixed, rounds, points, final_evals);
+    return radix_run_batch(ops, k, ns, fixed, rounds, points, final_evals);
     ZIGZ_NOTHROW_END(ctx)
 }
 
-// what zigz_sumcheck_prove[_interactive] / zigz_dev_sumcheck_prove would say about table i before running it
+// what zigz_sumcheck_prove[_interactive] / zigz_dev_sumcheck_prove would say about table i before running it (the radix passes
+// read 16-byte chunks)
 zigz_status table_check(size_t n, const void *table, bool dev, const uint64_t *fixed) {
-    if (dev && !table) return ZIGZ_ERR_INVALID_ARGUMENT;
-    CHK(mle_check(n));
-    if (n == 1) return ZIGZ_ERR_NO_VARIABLES;
-    if (!table) return ZIGZ_ERR_INVALID_ARGUMENT;
-    if (dev && !aligned16(table)) return ZIGZ_ERR_INVALID_ARGUMENT;  // (the radix passes read 16-byte chunks)
-    const size_t nv = log2_floor(n);
-    if (2 * (nv + 1) > 4096) return ZIGZ_ERR_INVALID_ARGUMENT;  // sumcheck_core
-    if (fixed)
-        for (size_t j = 0; j < nv; j++)
-            if (fixed[j] >= P) return ZIGZ_ERR_NOT_CANONICAL;
-    return ZIGZ_OK;
+    return table_rule(TableRule{dev, false, true, false, 63}, &table, 1, n, fixed);
 }
 
 }  // namespace
@@ -379,8 +270,9 @@ extern "C" zigz_status zigz_sumcheck_radix_run_batch(void *user, zigz_radix_batc
         if (fixed_challenges && !canonical(fixed_challenges + off, log2_floor(ns[i]))) return ZIGZ_ERR_NOT_CANONICAL;
         off += log2_floor(ns[i]);
     }
-    return radix_run_batch(nullptr, BatchOps{user, block_sums, fold, read_tail}, k, ns, fixed_challenges, rounds, points,
-                           final_evals);
+    ZIGZ_NOTHROW_BEGIN
+    return radix_run_batch(BatchOps{user, block_sums, fold, read_tail}, k, ns, fixed_challenges, rounds, points, final_evals);
+    ZIGZ_NOTHROW_END(nullptr)
 }
 
 extern "C" zigz_status zigz_dev_sumcheck_prove_batch(zigz_ctx *ctx, const uint32_t *const *d_tables, const size_t *ns, size_t k,
@@ -564,7 +456,7 @@ extern "C" zigz_status zigz_lasso_prove_batch(zigz_ctx *ctx, size_t k, const uin
     HIPCHK(ctx, hipMemcpyAsync(h_fp.data(), dfp, nfp * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (*hflag) {
-        set_err(ctx, "input contains a value >= p (not a canonical BabyBear element)");
+        set_err(ctx, "%s", NOT_CANONICAL_TEXT);
         for (size_t i = 0; i < k; i++)
             if (!lasso_canonical(inst[i])) return fail_at(bad_index, i, ZIGZ_ERR_NOT_CANONICAL);
         return ZIGZ_ERR_NOT_CANONICAL;

@@ -1,8 +1,12 @@
 #pragma once
 // Shared by the translation units behind the C ABI of libzigz_hip.so (include/zigz_hip.h) -- api.cpp (contexts, workspaces,
-// boundary conversion, transcript), api_mle.cpp (MLE ops, sumcheck), api_commit.cpp (Merkle trees, commit jobs), api_misc.cpp
-// (Lasso, the measurement hook): the context, its workspaces, the error macros and the helpers one unit needs from another.  No CPU fallback for field or hash work on the data path: the
-// only host arithmetic is the sequential SHA3 Fiat-Shamir sponge (K11) and O(v) scalar bookkeeping.
+// boundary conversion, transcript), api_mle.cpp (MLE ops, the GPU passes of the sumcheck), api_commit.cpp (Merkle trees, commit
+// jobs), api_misc.cpp (Lasso, the measurement hook), api_batch.cpp, api_merkle_batch.cpp, api_merkle_verify.cpp,
+// api_mle_batch.cpp, api_product.cpp (the batched entries): the context, its workspaces, the error macros and the helpers one
+// unit needs from another.  What needs no HIP lives in headers of its own, testable without a GPU: the host side of every
+// sumcheck in sumcheck_host.hpp (field helpers, argument rule, round step, tail rounds, radix schedules), the plans in
+// commit_plan.hpp, open_plan.hpp and verify_plan.hpp.  No CPU fallback for field or hash work on the data path: the only host
+// arithmetic is the sequential SHA3 Fiat-Shamir sponge (K11) and O(v) scalar bookkeeping.
 #include "zigz_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -17,12 +21,10 @@
 #include <thread>
 #include <vector>
 
-#include "batch_host.hpp"
 #include "commit_plan.hpp"
 #include "field.hpp"
-#include "host_hash.hpp"
-#include "host_parallel.hpp"
 #include "kernels.hpp"
+#include "sumcheck_host.hpp"  // (with batch_host.hpp, host_hash.hpp, host_parallel.hpp)
 
 using namespace zk;
 
@@ -99,9 +101,7 @@ struct zigz_ctx {
 };
 static const size_t FLUSH_BYTES = (size_t)1 << 30;
 static const size_t SUMS_SLOTS = 8192;  // [0, 4096): results of the API calls; [4096, 8192): scratch of the measurement hook
-constexpr unsigned RADIX_MAX_K = 10;     // 1024 block sums per radix sumcheck stage
 constexpr size_t RADIX_MIN_N = 1 << 11;  // smaller tables use the per-round form (one launch + read-back per round)
-constexpr size_t HOST_TAIL_MAX = 1024;
 static const size_t PIN_WORDS = 1 << 19;  // 4 MiB: the openings of a batched job (32 proofs x 43 x (24 + 33 v) bytes) fit the zero-copy path
 static const size_t ROOTS_MAX_COLS = 4096;
 constexpr unsigned BATCH_MAX = 32;  // proofs per batched commit job (kernels.hpp: ColSrcs)
@@ -141,7 +141,6 @@ constexpr unsigned BATCH_ARENA_MAX_NV = 20;  // largest table of the arena form 
     } while (0)
 
 inline bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
-inline unsigned log2_floor(size_t n) { unsigned l = 0; while (n > 1) { n >>= 1; l++; } return l; }
 inline size_t ceil_pow2(size_t n) { size_t v = 1; while (v < n) v <<= 1; return v; }
 constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -155,11 +154,9 @@ bool spin_wait(const unsigned long long *flag, unsigned long long seq);
 DoneFlag done_flag(zigz_ctx *ctx, int which);
 zigz_status wait_published(zigz_ctx *ctx, const DoneFlag &done);
 zigz_status pinned(zigz_ctx *ctx, size_t bytes, uint8_t **out);
-zigz_status fail_at(size_t *bad_index, size_t i, zigz_status st);
 zigz_status log_launch(zigz_ctx *ctx, int cls, uint64_t perms, hipEvent_t start, hipEvent_t stop, hipEvent_t first, double *dur_us);
 zigz_status upload_u64(zigz_ctx *ctx, const uint64_t *h_in, size_t n, uint32_t *d_out, bool reduce);
 zigz_status download_u64(zigz_ctx *ctx, const uint32_t *d_in, size_t n, uint64_t *h_out);
-zigz_status mle_check(size_t n);
 uint32_t host_to_mont(uint64_t canonical);
 zigz_status read_u64(zigz_ctx *ctx, const void *d_src, size_t words, uint64_t *dst);
 zigz_status dev_half_sums(zigz_ctx *ctx, const uint32_t *d_in, size_t n, uint64_t out[2]);
@@ -196,8 +193,26 @@ zigz_status build_trees(zigz_ctx *ctx, const uint32_t *d_vals, size_t val_stride
 zigz_status keccak_times_collect(zigz_ctx *ctx);
 size_t mle_batch_fill(const uint32_t *const *d_tables, const size_t *ns, size_t k, const uint64_t *points, bool reversed,
                       MleBatchTab *tab, uint32_t *f);
+// Host tables of a batched entry: table f (ns[f] values) is narrowed to `h` + at[f] (pinned; at = packed_offsets(ns, count)) --
+// the first value >= p ends the call: ZIGZ_ERR_NOT_CANONICAL with owner[f] (owner == nullptr: f) in *bad_index --, all of them
+// are uploaded in one copy into workspace `slot`, and d[f] is table f on the device
+zigz_status stage_host_tables(zigz_ctx *ctx, const uint64_t *const *tables, const size_t *ns, size_t count,
+                              const std::vector<size_t> &at, uint32_t *h, int slot, const size_t *owner,
+                              std::vector<const uint32_t *> &d, size_t *bad_index);
 extern std::atomic<int> g_sleep_wait;
 #pragma GCC visibility pop
+
+// a host table's value >= p: the same words in the context's last error whichever path found it
+constexpr const char *NOT_CANONICAL_TEXT = "input contains a value >= p (not a canonical BabyBear element)";
+// A host form's checks (batch_host.hpp: checks_in_call_order) with that text for a value >= p.  When all pass,
+// stage_host_tables checks the values as it narrows them, before anything is launched.
+template <class Check>
+zigz_status host_checks(zigz_ctx *ctx, const uint64_t *const *tables, const size_t *ns, size_t k, size_t *bad_index, Check check) {
+    bool value;
+    const zigz_status st = checks_in_call_order(tables, ns, k, bad_index, check, &value);
+    if (value) set_err(ctx, "%s", NOT_CANONICAL_TEXT);
+    return st;
+}
 
 constexpr size_t OPEN_CHUNK_BYTES = (size_t)32 << 20;  // staging per chunk of the many-openings host forms
 // The chunked hand-off of the many-openings host forms: launch(ci, &done) stages and queues chunk ci, whose kernel writes into

@@ -1,7 +1,6 @@
 // C ABI of libzigz_hip.so, part 2: the MLE operations (bind, round sums, eval) and the sumcheck provers (per-round, radix, sharded by
 // rows over several GPUs).  The only host arithmetic is the sequential SHA3 Fiat-Shamir sponge and O(v) scalar bookkeeping.
 #include "api_internal.hpp"
-#include "radix_host.hpp"
 
 using namespace zk;
 
@@ -285,7 +284,7 @@ zigz_status sumcheck_core(zigz_ctx *ctx, const uint32_t *d_in, size_t n, uint32_
     HIPCHK(ctx, hipGetLastError());
     uint64_t s[2];
     CHK(read_u64(ctx, ctx->d_sums, 2, s));
-    RadixProver sc;  // (its challenge step only)
+    SumcheckRounds sc;
     sc.rounds = rounds;
     sc.point = point;
     sc.fixed = fixed;
@@ -294,9 +293,8 @@ zigz_status sumcheck_core(zigz_ctx *ctx, const uint32_t *d_in, size_t n, uint32_
     size_t len = n;
     double bind_us = 0;
     for (size_t round = 0; round < nv; round++) {
-        uint64_t c0 = s[0] % P, s1 = s[1] % P;
-        uint64_t c1 = s1 >= c0 ? s1 - c0 : s1 + P - c0;  // roundPolynomial: [q(0), q(1)-q(0)], multilinear.zig:228-229
-        const uint64_t ch = sc.challenge(c0, c1);
+        const uint64_t c[2] = {s[0] % P, f_sub(s[1] % P, s[0] % P)};  // roundPolynomial: [q(0), q(1)-q(0)], multilinear.zig:228-229
+        const uint64_t ch = sc.step(c);
         CHK(sc.st);
         uint32_t *dst = (round % 2 == 0) ? bufA : bufB;
         const bool last = (len == 2);
@@ -337,128 +335,18 @@ zigz_status sumcheck_core(zigz_ctx *ctx, const uint32_t *d_in, size_t n, uint32_
 //   pass 2  GPU: T'[i] = sum_b eq(r_0..r_{k-1}; b) * T[b*m + i]  (one more read, writes n/2^k) + next block sums
 // i.e. two passes over the table per k <= 10 rounds and two host round trips instead of k.  The O(n) data work
 // stays on the GPU; the host touches only the <= 1024-entry sums tables (and the final <= 1024-entry table).
-// Exact field arithmetic => identical round polynomials, challenges and final_eval (tests compare both forms).  The host
-// rounds are radix_host.hpp's, shared with the batched prover.
+// Exact field arithmetic => identical round polynomials, challenges and final_eval (tests compare both forms).  The schedule
+// and the host rounds are sumcheck_host.hpp's (radix_run), shared with the batched prover; here are its three passes on the GPU.
 
-// The radix sumcheck as orchestration over three data passes (RadixOps) and, when the table is sharded by rows over
-// several GPUs, one exchange hook.  Row sharding: global index i lives on rank i mod G at local index
-// i / G, so the MSB-first bind pairs (i, i + n/2) of the first v - log2 G rounds are rank-local, the top k index bits
-// of i are the top k bits of the local index -- a rank's block sums are its share of the global block sums -- and the
-// fold T'[i'] = sum_b eq_b T[b*m + i'] is rank-local too.  Per stage of k <= 10 rounds the ranks exchange 2^k <= 1024
-// exact u64 partial sums (ONE all-gather, added locally = an all-reduce), and once the local tables are <= 1024
-// entries one all-gather re-assembles the remaining table (local index j of rank g -> global index j*G + g) that
-// every rank finishes identically.  2-3 exchanges per proof instead of one per round; transcripts run in lockstep.
 namespace {
-struct RadixOps {
-    void *user;
-    // exact u64 sums of the 2^k contiguous blocks of the current local table
-    zigz_status (*block_sums)(void *user, unsigned k, uint64_t *sums);
-    // current := fold of the current table with the 2^k canonical weights (length / 2^k entries); when k_next != 0 also
-    // the exact u64 sums of the 2^k_next blocks of the result
-    zigz_status (*fold)(void *user, unsigned k, const uint64_t *weights, unsigned k_next, uint64_t *next_sums);
-    // the current local table (m canonical values)
-    zigz_status (*read_tail)(void *user, size_t m, uint64_t *out);
-};
-struct ShardComm {
-    int rank, world;
-    zigz_allgather_fn allgather;
-    void *user;
-    bool sums_global;  // the data passes already return the sums over ALL ranks (reduced on the device: RCCL all-reduce)
-};
-
-zigz_status radix_run(zigz_ctx *ctx, const RadixOps &ops, size_t n_local, const ShardComm *comm, const uint64_t *fixed,
-                      uint64_t *rounds, uint64_t *point, uint64_t *final_eval) {
+// radix_run at the ABI boundary: its error text into the context's last error, no exception through the C ABI
+zigz_status radix_run_ctx(zigz_ctx *ctx, const RadixOps &ops, size_t n_local, const ShardComm *comm, const uint64_t *fixed,
+                          uint64_t *rounds, uint64_t *point, uint64_t *final_eval) {
     ZIGZ_NOTHROW_BEGIN
-    const size_t world = comm && comm->world > 1 ? (size_t)comm->world : 1;
-    RadixProver s;
-    s.len = n_local;
-    s.nv = log2_floor(n_local) + log2_floor(world);  // (the rank bits are variables too)
-    s.rounds = rounds;
-    s.point = point;
-    s.fixed = fixed;
-    std::vector<uint64_t> gather, wire;
-    // One exchange: every rank contributes `v` (all ranks the same length) behind ONE status word.  A rank whose local pass
-    // failed still takes part -- with its status and a zero payload -- so that all ranks leave the proof at the same
-    // exchange: the failing rank with its own error, the others with ZIGZ_ERR_COMM (instead of sitting in the transport's
-    // timeout while the failed rank has long returned).
-    zigz_status local = ZIGZ_OK;
-    auto exchange = [&](const std::vector<uint64_t> &v) -> zigz_status {  // gather := world x v
-        const size_t n = v.size();
-        wire.assign(n + 1, 0);
-        wire[0] = (uint64_t)(uint32_t)local;
-        if (local == ZIGZ_OK) memcpy(wire.data() + 1, v.data(), n * 8);
-        std::vector<uint64_t> all(world * (n + 1));
-        if (!comm->allgather || comm->allgather(comm->user, wire.data(), (n + 1) * 8, all.data()) != 0) {
-            set_err(ctx, "sharded sumcheck: the all-gather hook failed");
-            return local != ZIGZ_OK ? local : ZIGZ_ERR_COMM;
-        }
-        gather.resize(world * n);
-        bool peer_failed = false;
-        for (size_t r = 0; r < world; r++) {
-            if (all[r * (n + 1)] != ZIGZ_OK) peer_failed = true;
-            memcpy(gather.data() + r * n, all.data() + r * (n + 1) + 1, n * 8);
-        }
-        if (local != ZIGZ_OK) return local;
-        if (peer_failed) {
-            set_err(ctx, "sharded sumcheck: another rank reported an error");
-            return ZIGZ_ERR_COMM;
-        }
-        return ZIGZ_OK;
-    };
-    // a local data pass: alone, its status is returned at once; sharded, it is carried into the next exchange
-#define ZK_LOCAL(expr)                                     \
-    do {                                                   \
-        if (local == ZIGZ_OK) local = (expr);              \
-        if (local != ZIGZ_OK && world == 1) return local;  \
-    } while (0)
-    // partial sums of every rank -> totals (exact: < 2^31 * 2^40 per rank, a few ranks)
-    auto sum_over_ranks = [&](std::vector<uint64_t> &v) -> zigz_status {
-        if (world == 1 || comm->sums_global) return ZIGZ_OK;
-        CHK(exchange(v));
-        for (size_t i = 0; i < v.size(); i++) {
-            uint64_t t = 0;
-            for (size_t r = 0; r < world; r++) t += gather[r * v.size() + i];
-            v[i] = t;
-        }
-        return ZIGZ_OK;
-    };
-    if ((s.k = radix_stage_k(s.len))) {
-        s.B.assign((size_t)1 << s.k, 0);
-        ZK_LOCAL(ops.block_sums(ops.user, s.k, s.B.data()));
-        CHK(sum_over_ranks(s.B));
-        for (;;) {
-            s.stage_rounds();
-            CHK(s.st);
-            const size_t m = s.len >> s.k;
-            const unsigned k_next = radix_stage_k(m);
-            s.B.assign(k_next ? (size_t)1 << k_next : 0, 0);
-            ZK_LOCAL(ops.fold(ops.user, s.k, s.W.data(), k_next, k_next ? s.B.data() : nullptr));
-            s.len = m;
-            if (!k_next) break;
-            CHK(sum_over_ranks(s.B));
-            s.k = k_next;
-        }
-    }
-    // the remaining table: len local entries per rank, global index j*G + g
-    const size_t len = s.len;
-    std::vector<uint64_t> mine(len), tail;
-    ZK_LOCAL(ops.read_tail(ops.user, len, mine.data()));
-#undef ZK_LOCAL
-    if (world == 1) {
-        tail.swap(mine);
-    } else {
-        CHK(exchange(mine));
-        tail.resize(world * len);
-        for (size_t r = 0; r < world; r++)
-            for (size_t j = 0; j < len; j++) {
-                if (gather[r * len + j] >= P) return ZIGZ_ERR_NOT_CANONICAL;  // (the same verdict on every rank)
-                tail[j * world + r] = gather[r * len + j];
-            }
-    }
-    const uint64_t fe = s.tail_rounds(tail);  // the last rounds on the <= 1024 * G entry table, identical on every rank
-    CHK(s.st);
-    *final_eval = fe;
-    return ZIGZ_OK;
+    const char *err = nullptr;
+    const zigz_status st = radix_run(ops, n_local, comm, fixed, rounds, point, final_eval, &err);
+    if (err) set_err(ctx, "%s", err);
+    return st;
     ZIGZ_NOTHROW_END(ctx)
 }
 
@@ -633,7 +521,7 @@ static zigz_status sumcheck_radix_sharded(zigz_ctx *ctx, const uint32_t *d_in, s
     // both regions of the stage sums zero before the first pass (one fill per sumcheck; every read-back re-zeroes what it read)
     if (!rccl && n > HOST_TAIL_MAX) HIPCHK(ctx, hipMemsetAsync(ctx->d_sums, 0, (2048 + ((size_t)1 << RADIX_MAX_K) + 1) * 8, ctx->stream));
     const RadixOps ops{&g, gpu_block_sums, gpu_fold, gpu_read_tail};
-    return radix_run(ctx, ops, n, comm, fixed, rounds, point, final_eval);
+    return radix_run_ctx(ctx, ops, n, comm, fixed, rounds, point, final_eval);
 }
 
 static zigz_status sumcheck_radix(zigz_ctx *ctx, const uint32_t *d_in, size_t n, const uint64_t *fixed, uint64_t *rounds,
@@ -647,9 +535,7 @@ extern "C" zigz_status zigz_dev_sumcheck_prove_sharded(zigz_ctx *ctx, const uint
                                                        uint64_t *rounds, uint64_t *point, uint64_t *final_eval) {
     ZIGZ_ENTER(ctx);
     if (!ctx || !d_local || !rounds || !point || !final_eval) return ZIGZ_ERR_INVALID_ARGUMENT;
-    CHK(mle_check(n_local));
-    if (world < 1 || rank < 0 || rank >= world || !is_pow2((size_t)world) || (world > 1 && !allgather)) return ZIGZ_ERR_INVALID_ARGUMENT;
-    if (n_local * (size_t)world == 1) return ZIGZ_ERR_NO_VARIABLES;
+    CHK(shard_check(n_local, rank, world, allgather != nullptr));
     if (!aligned16(d_local)) return ZIGZ_ERR_INVALID_ARGUMENT;
     const ShardComm comm{rank, world, allgather, user, false};
     return sumcheck_radix_sharded(ctx, d_local, n_local, &comm, nullptr, rounds, point, final_eval);
@@ -663,10 +549,8 @@ extern "C" zigz_status zigz_dev_sumcheck_prove_rccl(zigz_ctx *ctx, const uint32_
                                                     uint64_t *rounds, uint64_t *point, uint64_t *final_eval) {
     ZIGZ_ENTER(ctx);
     if (!ctx || !d_local || !rccl || !rounds || !point || !final_eval) return ZIGZ_ERR_INVALID_ARGUMENT;
-    CHK(mle_check(n_local));
     const int world = zigz_rccl_comm_world(rccl), rank = zigz_rccl_comm_rank(rccl);
-    if (world < 1 || !is_pow2((size_t)world)) return ZIGZ_ERR_INVALID_ARGUMENT;
-    if (n_local * (size_t)world == 1) return ZIGZ_ERR_NO_VARIABLES;
+    CHK(shard_check(n_local, rank, world, true));
     if (!aligned16(d_local)) return ZIGZ_ERR_INVALID_ARGUMENT;
     const ShardComm comm{rank, world, zigz_rccl_allgather, rccl, true};
     // (one rank: the all-reduce is RCCL's identity, and the path is the one several ranks take)
@@ -674,30 +558,25 @@ extern "C" zigz_status zigz_dev_sumcheck_prove_rccl(zigz_ctx *ctx, const uint32_
 }
 
 // The orchestration alone, over caller-supplied data passes (multi-process tests on CPU drive exactly the code path of
-// zigz_dev_sumcheck_prove_sharded with stand-in passes; a host with its own kernels could do the same)
+// zigz_dev_sumcheck_prove_sharded with stand-in passes; a host with its own kernels could do the same).  sums_global: the passes
+// return the sums over ALL ranks already (reduced inside the pass, as the RCCL passes above do).
+static zigz_status radix_run_entry(const zigz_radix_ops *ops, size_t n_local, int rank, int world, zigz_allgather_fn allgather,
+                                   void *comm_user, bool sums_global, const uint64_t *fixed_challenges, uint64_t *rounds,
+                                   uint64_t *point, uint64_t *final_eval) {
+    if (!ops || !ops->block_sums || !ops->fold || !ops->read_tail || !rounds || !point || !final_eval) return ZIGZ_ERR_INVALID_ARGUMENT;
+    CHK(shard_check(n_local, rank, world, allgather != nullptr));
+    const ShardComm comm{rank, world, allgather, comm_user, sums_global};
+    return radix_run_ctx(nullptr, *ops, n_local, &comm, fixed_challenges, rounds, point, final_eval);
+}
 extern "C" zigz_status zigz_sumcheck_radix_run(const zigz_radix_ops *ops, size_t n_local, int rank, int world,
                                                zigz_allgather_fn allgather, void *comm_user, const uint64_t *fixed_challenges,
                                                uint64_t *rounds, uint64_t *point, uint64_t *final_eval) {
-    if (!ops || !ops->block_sums || !ops->fold || !ops->read_tail || !rounds || !point || !final_eval) return ZIGZ_ERR_INVALID_ARGUMENT;
-    CHK(mle_check(n_local));
-    if (world < 1 || rank < 0 || rank >= world || !is_pow2((size_t)world) || (world > 1 && !allgather)) return ZIGZ_ERR_INVALID_ARGUMENT;
-    if (n_local * (size_t)world == 1) return ZIGZ_ERR_NO_VARIABLES;
-    const ShardComm comm{rank, world, allgather, comm_user, false};
-    const RadixOps r{ops->user, ops->block_sums, ops->fold, ops->read_tail};
-    return radix_run(nullptr, r, n_local, &comm, fixed_challenges, rounds, point, final_eval);
+    return radix_run_entry(ops, n_local, rank, world, allgather, comm_user, false, fixed_challenges, rounds, point, final_eval);
 }
-
-// ... for data passes that return the sums over ALL ranks already (reduced inside the pass, as the RCCL passes above do)
 extern "C" zigz_status zigz_sumcheck_radix_run_reduced(const zigz_radix_ops *ops, size_t n_local, int rank, int world,
                                                        zigz_allgather_fn allgather, void *comm_user, const uint64_t *fixed_challenges,
                                                        uint64_t *rounds, uint64_t *point, uint64_t *final_eval) {
-    if (!ops || !ops->block_sums || !ops->fold || !ops->read_tail || !rounds || !point || !final_eval) return ZIGZ_ERR_INVALID_ARGUMENT;
-    CHK(mle_check(n_local));
-    if (world < 1 || rank < 0 || rank >= world || !is_pow2((size_t)world) || (world > 1 && !allgather)) return ZIGZ_ERR_INVALID_ARGUMENT;
-    if (n_local * (size_t)world == 1) return ZIGZ_ERR_NO_VARIABLES;
-    const ShardComm comm{rank, world, allgather, comm_user, true};
-    const RadixOps r{ops->user, ops->block_sums, ops->fold, ops->read_tail};
-    return radix_run(nullptr, r, n_local, &comm, fixed_challenges, rounds, point, final_eval);
+    return radix_run_entry(ops, n_local, rank, world, allgather, comm_user, true, fixed_challenges, rounds, point, final_eval);
 }
 
 extern "C" zigz_status zigz_dev_sumcheck_prove(zigz_ctx *ctx, const uint32_t *d_in, size_t n, uint32_t *d_scratch,
@@ -744,9 +623,8 @@ extern "C" zigz_status zigz_mle_round_poly(zigz_ctx *ctx, const uint64_t *in, si
     CHK(stage_in(ctx, in, n, &d_in));
     uint64_t s[2];
     CHK(dev_half_sums(ctx, d_in, n, s));
-    uint64_t s0 = s[0] % P, s1 = s[1] % P;
-    out[0] = s0;
-    out[1] = s1 >= s0 ? s1 - s0 : s1 + P - s0;
+    out[0] = s[0] % P;
+    out[1] = f_sub(s[1] % P, out[0]);
     return ZIGZ_OK;
 }
 
@@ -759,7 +637,7 @@ extern "C" zigz_status zigz_mle_sum(zigz_ctx *ctx, const uint64_t *in, size_t n,
     CHK(stage_in(ctx, in, n, &d_in));
     uint64_t s[2];
     CHK(dev_half_sums(ctx, d_in, n, s));
-    *out = (s[0] % P + s[1] % P) % P;
+    *out = f_add(s[0] % P, s[1] % P);
     return ZIGZ_OK;
 }
 

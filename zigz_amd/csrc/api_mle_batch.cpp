@@ -31,7 +31,7 @@ size_t mle_batch_fill(const uint32_t *const *d_tables, const size_t *ns, size_t 
         tab[i] = t;
         for (unsigned v = 0; v < nv; v++) {
             const uint64_t r = points[off + (reversed ? nv - 1 - v : v)];
-            f[2 * (off + v)] = host_to_mont((1 + P - r) % P);
+            f[2 * (off + v)] = host_to_mont(f_sub(1, r));
             f[2 * (off + v) + 1] = host_to_mont(r);
         }
         off += nv;
@@ -48,14 +48,6 @@ struct Layout {
     size_t desc_off = 0, f_off = 0, stage_bytes = 0, tab_off = 0, tab_words = 0, bytes = 0;
     std::vector<size_t> at;  // host forms: table i's first word among the narrowed tables (every table 16-byte aligned)
 };
-
-// a host table's value >= p at table i: the same words in the context's last error whichever path found it
-constexpr const char *NOT_CANONICAL_TEXT = "input contains a value >= p (not a canonical BabyBear element)";
-
-zigz_status not_canonical(zigz_ctx *ctx, size_t *bad_index, size_t i) {
-    set_err(ctx, "%s", NOT_CANONICAL_TEXT);
-    return fail_at(bad_index, i, ZIGZ_ERR_NOT_CANONICAL);
-}
 
 // ns[i] are powers of two <= 2^32 (checked by the callers)
 zigz_status plan(const size_t *ns, size_t k, bool host_tables, Layout &L) {
@@ -95,31 +87,6 @@ zigz_status eval_queue(zigz_ctx *ctx, const Layout &L, uint8_t *pin, const uint3
     return ZIGZ_OK;
 }
 
-// Host tables: narrowed into the pinned region (the first value >= p ends it: its table's index to *bad_index) and uploaded in
-// one copy; d[i] = table i on the device.
-zigz_status upload_tables(zigz_ctx *ctx, const Layout &L, uint8_t *pin, const uint64_t *const *tables, const size_t *ns,
-                          std::vector<const uint32_t *> &d, size_t *bad_index) {
-    uint32_t *h = (uint32_t *)(pin + L.tab_off);
-    for (size_t i = 0; i < L.k; i++)
-        if (!narrow(tables[i], ns[i], h + L.at[i])) return not_canonical(ctx, bad_index, i);
-    void *d32;
-    CHK(ws_get(ctx, WS_MLEBATCH_IN, L.tab_words * 4, &d32));
-    HIPCHK(ctx, hipMemcpyAsync(d32, h, L.tab_words * 4, hipMemcpyHostToDevice, ctx->stream));
-    d.resize(L.k);
-    for (size_t i = 0; i < L.k; i++) d[i] = (const uint32_t *)d32 + L.at[i];
-    return ZIGZ_OK;
-}
-
-// A host form's checks (batch_host.hpp: checks_in_call_order) with this file's error text for a value >= p.  When all pass,
-// upload_tables checks the values as it narrows them, before anything is launched.
-template <class Check>
-zigz_status host_checks(zigz_ctx *ctx, const uint64_t *const *tables, const size_t *ns, size_t k, size_t *bad_index, Check check) {
-    bool value;
-    const zigz_status st = checks_in_call_order(tables, ns, k, bad_index, check, &value);
-    if (value) set_err(ctx, "%s", NOT_CANONICAL_TEXT);
-    return st;
-}
-
 zigz_status eval_batch(zigz_ctx *ctx, const uint32_t *const *d_tables, const uint64_t *const *h_tables, const size_t *ns, size_t k,
                        const uint64_t *points, uint64_t *out, size_t *bad_index) {
     ZIGZ_NOTHROW_BEGIN
@@ -129,7 +96,7 @@ zigz_status eval_batch(zigz_ctx *ctx, const uint32_t *const *d_tables, const uin
     CHK(pinned(ctx, L.bytes, &pin));
     std::vector<const uint32_t *> d;
     if (h_tables) {
-        CHK(upload_tables(ctx, L, pin, h_tables, ns, d, bad_index));
+        CHK(stage_host_tables(ctx, h_tables, ns, k, L.at, (uint32_t *)(pin + L.tab_off), WS_MLEBATCH_IN, nullptr, d, bad_index));
         d_tables = d.data();
     }
     DoneFlag done;
@@ -151,7 +118,7 @@ zigz_status verify_batch(zigz_ctx *ctx, const uint32_t *const *d_tables, const u
     CHK(pinned(ctx, L.bytes, &pin));
     std::vector<const uint32_t *> d;
     if (h_tables) {
-        CHK(upload_tables(ctx, L, pin, h_tables, ns, d, bad_index));
+        CHK(stage_host_tables(ctx, h_tables, ns, k, L.at, (uint32_t *)(pin + L.tab_off), WS_MLEBATCH_IN, nullptr, d, bad_index));
         d_tables = d.data();
     }
     DoneFlag done;

@@ -6,19 +6,16 @@
 // the sums into coefficients and steps every live transcript on its threads.  Every later round is the same copy and two
 // launches with the fused bind pass in place of the sums (the first one writes each factor's bound copy, n/2 words, into the
 // workspace; the later ones run in place there); an instance leaves the live set when its tables are 1024 long.  One launch
-// then hands the current tables of ALL instances to the host, which finishes their rounds (product_host.hpp).
+// then hands the current tables of ALL instances to the host, which finishes their rounds (sumcheck_host.hpp).
 #include "api_internal.hpp"
 #include "product_host.hpp"
 
 using namespace zk;
 
-static_assert(pd::TAIL_MAX == HOST_TAIL_MAX, "the product prover hands over at the linear prover's tail length");
 static_assert(pd::MAX_DEGREE == PRODUCT_MAX_DEGREE && ZIGZ_PRODUCT_MAX_LOG2_N == PRODUCT_MAX_LOG2_N, "header, host and kernels");
 static_assert(pd::R1 == R_MOD_P && pd::R2 == R2_MOD_P, "the host's scales are powers of the kernels' R");
 
 namespace {
-
-constexpr const char *NOT_CANONICAL_TEXT = "input contains a value >= p (not a canonical BabyBear element)";
 
 struct Inst {
     unsigned d = 0;
@@ -26,7 +23,7 @@ struct Inst {
     const uint32_t *cur[PRODUCT_MAX_DEGREE] = {};
     uint32_t *work[PRODUCT_MAX_DEGREE] = {};
     uint64_t ch = 0;  // the challenge of the instance's last round
-    pd::Prover pr;
+    SumcheckRounds pr;
 };
 
 // one call's pinned region: sums (PRODUCT_SUMS u64 per instance) | tails (u32) | round descriptors | tail descriptors | the
@@ -34,18 +31,19 @@ struct Inst {
 struct Layout {
     size_t tail_off = 0, tail_words = 0, desc_off = 0, tdesc_off = 0, tab_off = 0, tab_words = 0, bytes = 0;
     size_t nwg = 0, work_words = 0;  // workgroups of round 0; words of all bound copies
+    std::vector<size_t> fns, owner;  // every factor's length and instance
     std::vector<size_t> at;          // host form: factor f's first word among the narrowed tables (each 16-byte aligned)
 };
 
 zigz_status plan(size_t k, const unsigned *degrees, const size_t *ns, bool host_tables, Layout &L) {
-    std::vector<size_t> fns;
     for (size_t i = 0; i < k; i++) {
-        L.tail_words += degrees[i] * (ns[i] < pd::TAIL_MAX ? ns[i] : pd::TAIL_MAX);
-        if (ns[i] > pd::TAIL_MAX) {
+        L.tail_words += degrees[i] * (ns[i] < HOST_TAIL_MAX ? ns[i] : HOST_TAIL_MAX);
+        if (ns[i] > HOST_TAIL_MAX) {
             L.nwg += product_wgs(ns[i]);
             L.work_words += degrees[i] * (ns[i] / 2);
         }
-        for (unsigned j = 0; j < degrees[i]; j++) fns.push_back(ns[i]);
+        L.fns.insert(L.fns.end(), degrees[i], ns[i]);
+        L.owner.insert(L.owner.end(), degrees[i], i);
     }
     if (L.nwg > MLE_BATCH_MAX_WGS) return ZIGZ_ERR_INVALID_ARGUMENT;  // one launch: fewer than 2^32 threads in its grid
     const size_t desc = align256(k * sizeof(ProductTab));
@@ -54,8 +52,8 @@ zigz_status plan(size_t k, const unsigned *degrees, const size_t *ns, bool host_
     L.tdesc_off = L.desc_off + desc;
     L.tab_off = L.tdesc_off + desc;
     if (host_tables) {
-        L.at = packed_offsets(fns.data(), fns.size());
-        L.tab_words = L.at[fns.size()];
+        L.at = packed_offsets(L.fns.data(), L.fns.size());
+        L.tab_words = L.at[L.fns.size()];
     }
     L.bytes = L.tab_off + L.tab_words * 4;
     return ZIGZ_OK;
@@ -70,19 +68,9 @@ zigz_status run(zigz_ctx *ctx, size_t k, const unsigned *degrees, const uint32_t
     uint8_t *pin;
     CHK(pinned(ctx, L.bytes, &pin));
     std::vector<const uint32_t *> up;
-    if (h_factors) {  // narrowed into the pinned region (the first value >= p ends the call) and uploaded in one copy
-        uint32_t *h = (uint32_t *)(pin + L.tab_off);
-        for (size_t i = 0, f = 0; i < k; i++)
-            for (unsigned j = 0; j < degrees[i]; j++, f++)
-                if (!narrow(h_factors[f], ns[i], h + L.at[f])) {
-                    set_err(ctx, "%s", NOT_CANONICAL_TEXT);
-                    return fail_at(bad_index, i, ZIGZ_ERR_NOT_CANONICAL);
-                }
-        void *d32;
-        CHK(ws_get(ctx, WS_PRODUCT_IN, L.tab_words * 4, &d32));
-        HIPCHK(ctx, hipMemcpyAsync(d32, h, L.tab_words * 4, hipMemcpyHostToDevice, ctx->stream));
-        up.resize(L.at.size() - 1);
-        for (size_t f = 0; f + 1 < L.at.size(); f++) up[f] = (const uint32_t *)d32 + L.at[f];
+    if (h_factors) {
+        CHK(stage_host_tables(ctx, h_factors, L.fns.data(), L.fns.size(), L.at, (uint32_t *)(pin + L.tab_off), WS_PRODUCT_IN,
+                              L.owner.data(), up, bad_index));
         d_factors = up.data();
     }
     const size_t desc = L.tdesc_off - L.desc_off;
@@ -103,15 +91,15 @@ zigz_status run(zigz_ctx *ctx, size_t k, const unsigned *degrees, const uint32_t
             s.d = degrees[i];
             s.len = ns[i];
             s.tail_off = toff;
-            toff += s.d * (ns[i] < pd::TAIL_MAX ? ns[i] : pd::TAIL_MAX);
+            toff += s.d * (ns[i] < HOST_TAIL_MAX ? ns[i] : HOST_TAIL_MAX);
             for (unsigned j = 0; j < s.d; j++) {
                 s.cur[j] = d_factors[foff + j];
-                if (ns[i] > pd::TAIL_MAX) {  // every factor's bound copy is 16-byte aligned: n / 2 >= 1024 words
+                if (ns[i] > HOST_TAIL_MAX) {  // every factor's bound copy is 16-byte aligned: n / 2 >= 1024 words
                     s.work[j] = (uint32_t *)d_work + woff;
                     woff += ns[i] / 2;
                 }
             }
-            s.pr.d = s.d;
+            s.pr.ncoef = s.d + 1;
             s.pr.nv = log2_floor(ns[i]);
             s.pr.claimed_sum = claimed_sums + i;
             s.pr.rounds = rounds + roff;
@@ -120,7 +108,7 @@ zigz_status run(zigz_ctx *ctx, size_t k, const unsigned *degrees, const uint32_t
             foff += s.d;
             voff += s.pr.nv;
             roff += (size_t)(s.d + 1) * s.pr.nv;
-            if (ns[i] > pd::TAIL_MAX) live.push_back(i);
+            if (ns[i] > HOST_TAIL_MAX) live.push_back(i);
         }
     }
     // the live instances' descriptors for one pass; returns its workgroup count
@@ -149,7 +137,7 @@ zigz_status run(zigz_ctx *ctx, size_t k, const unsigned *degrees, const uint32_t
             Inst &s = t[who[x]];
             uint64_t c[PRODUCT_SUMS];
             pd::coefficients(s.d, h_sums + PRODUCT_SUMS * who[x], c);
-            s.ch = s.pr.challenge(c);
+            s.ch = s.pr.step(c);
         });
     };
     if (!live.empty()) {  // round 0: sums over the caller's tables
@@ -169,7 +157,7 @@ zigz_status run(zigz_ctx *ctx, size_t k, const unsigned *degrees, const uint32_t
             Inst &s = t[i];
             for (unsigned j = 0; j < s.d; j++) s.cur[j] = s.work[j];
             s.len /= 2;
-            if (s.len > pd::TAIL_MAX) next.push_back(i);
+            if (s.len > HOST_TAIL_MAX) next.push_back(i);
         }
         HIPCHK(ctx, hipMemcpyAsync(d_stage, h_desc, live.size() * sizeof(ProductTab), hipMemcpyHostToDevice, ctx->stream));
         launch_product_bind(d_desc, (unsigned)live.size(), wg, d_part, ctx->stream);
