@@ -628,6 +628,78 @@ zigz_status zigz_sumcheck_prove_product_batch(zigz_ctx *ctx, size_t k, const uns
                                               uint64_t *points, uint64_t *factor_evals, uint64_t *final_evals,
                                               size_t *bad_index);
 
+/* k eq tables in ONE launch: table i has ns[i] = 2^v_i canonical words
+ *   E_i[x] = prod_{j < v_i} (bit j of x ? tau_j : 1 - tau_j),
+ * tau the v_i coordinates at points + sum_{j<i} v_j (concatenated in table order).  point[0] goes with the LSB of the index,
+ * Multilinear.eval's convention (multilinear.zig:110-144): sum_x E_i[x] T[x] == zigz_dev_mle_eval(T, ns[i], tau, v_i) exactly, and
+ * ns[i] == 1 gives the one-word table {1}.  With E_tau as the first factor, zigz_dev_sumcheck_prove_product_batch proves the
+ * zero-check sum_x eq(tau, x) C(x) = 0 of a constraint C that is a product of up to two tables (the degree-3 rounds of
+ * src/prover/prover.zig:237-288), and zigz_dev_sumcheck_verify_product_batch verifies it without the table.
+ * d_out[i]: ns[i] packed u32 words of device memory, 16-byte aligned; nothing behind them is written.  Schedule: one small copy
+ * (descriptors and factor pairs) and one launch for all k tables, queued on the context's stream; the call does not wait for
+ * them -- the caller's next launch on the same stream sees the tables.
+ * Every argument is checked for every table before anything is launched or written; the first failing table's index goes to
+ * *bad_index (if non-NULL): ZIGZ_ERR_INVALID_ARGUMENT for ctx, ns, points or d_out NULL, k > ZIGZ_BATCH_MAX, an output that is
+ * NULL or not 16-byte aligned, ns[i] > 2^32, or tables that together make 2^24 chunks of 8192 words or more (one launch's grid);
+ * ZIGZ_ERR_EMPTY_EVALUATIONS / ZIGZ_ERR_LENGTH_NOT_POWER_OF_TWO for the length; ZIGZ_ERR_NOT_CANONICAL for a coordinate >= p.
+ * k == 0 returns ZIGZ_OK and touches nothing.  Leaves the hint options, zigz_kernel_stats, an active commit job and open
+ * zigz_merkle_batch handles alone. */
+zigz_status zigz_dev_eq_table_batch(zigz_ctx *ctx, size_t k, const size_t *ns, const uint64_t *points, uint32_t *const *d_out,
+                                    size_t *bad_index);
+/* the same into host arrays of ns[i] canonical u64 words: built on the device, downloaded through pinned memory in chunks of at
+ * most 32 MiB and widened on the way; returns when out is written */
+zigz_status zigz_eq_table_batch(zigz_ctx *ctx, size_t k, const size_t *ns, const uint64_t *points, uint64_t *const *out,
+                                size_t *bad_index);
+
+/* k independent verifications of the proofs zigz_dev_sumcheck_prove_product_batch writes: SumcheckVerifier.verify
+ * (src/proofs/sumcheck_verifier.zig:48-108, verifyRounds :172-205) with d + 1 coefficients per round, the oracle being the
+ * product of the proof's d factors.  Proof i, in the prover's layout: degrees[i] = d_i in 1..ZIGZ_PRODUCT_MAX_DEGREE, ns[i] =
+ * 2^v_i, rounds ((d_i + 1) v_i words, c_0..c_d per round), points (v_i), factor_evals (d_i; the array may be NULL) and
+ * final_evals[i], claimed_sums[i]; everything concatenated in proof order.
+ * FACTORS.  d_factors holds sum d_i pointers, proof by proof; factor_kinds (sum d_i bytes, or NULL: all tables) says what each
+ * is: ZIGZ_FACTOR_TABLE -- the table at d_factors (ns[i] packed u32 words, 16-byte aligned); ZIGZ_FACTOR_EQ -- eq(tau, .), the
+ * table zigz_dev_eq_table_batch would build, WITHOUT the table: its d_factors entry must be NULL and its tau is the next v_i words
+ * of eq_points (the taus of all eq factors concatenated in factor order).
+ * Per proof, bit for bit the reference: a fresh transcript, claim = claimed_sums[i]; per round reject if g(0) + g(1) != claim,
+ * absorb c_0..c_d in order, draw the challenge (sumcheck_protocol.zig:176-184), claim = g(challenge).  Then every factor's
+ * multilinear extension is evaluated at q -- the proof's point as given (flags == 0: the reference's behaviour, which REJECTS
+ * honest proofs of two or more variables in general, see zigz_dev_sumcheck_verify_batch) or reversed
+ * (ZIGZ_SUMCHECK_VERIFY_POINT_REVERSED: where the prover's evaluations live) --: table factors in the batched eval's launch, one
+ * (table, q) pair per factor, all proofs together; eq factors on the host in closed form, prod_j (tau_j q_j + (1 - tau_j)(1 -
+ * q_j)).  The proof is accepted iff the rounds held, prod_j oracle_j == claim, prod_j oracle_j == final_evals[i] and, when
+ * factor_evals != NULL, oracle_j == factor_evals[j] for every j.  (A zero-check's soundness also needs claimed_sums[i] == 0:
+ * that comparison is the caller's.)
+ * Outputs: verdicts[k] (may be NULL) 1 accept / 0 reject; *n_rejected; expected_evals[k] (may be NULL) the claim at the failing
+ * round, or the final claim; oracle_evals (sum d_i words, may be NULL) every factor's evaluation, written for every proof
+ * including those whose rounds failed.  For d_i == 1, a table factor and factor_evals == NULL these are
+ * zigz_dev_sumcheck_verify_batch's values.
+ * Schedule: the evaluation of all table factors is queued first, the host replays the k transcripts and computes the eq
+ * factors on its threads meanwhile, and combines after the hand-off; a call without a table factor launches nothing.
+ * Statuses are for the shape of the arguments only, never for what a proof holds; everything is checked for every proof
+ * before anything is launched or written, and the first failing proof's index goes to *bad_index (if non-NULL):
+ * ZIGZ_ERR_INVALID_ARGUMENT for ctx or n_rejected NULL, an unknown flag, a NULL input array when k > 0 (factor_kinds, eq_points
+ * and factor_evals excepted), k > ZIGZ_BATCH_MAX, a degree outside 1..ZIGZ_PRODUCT_MAX_DEGREE, an unknown kind, an eq factor
+ * whose pointer is not NULL or that has no eq_points, a table factor that is NULL or not 16-byte aligned, ns[i] > 2^32, or table
+ * factors that together make 2^24 chunks of 8192 elements or more; the prover's rules per table (ns[i] == 1 is
+ * ZIGZ_ERR_NO_VARIABLES); ZIGZ_ERR_NOT_CANONICAL for any word of a proof or of a tau >= p.  k == 0: ZIGZ_OK, *n_rejected = 0,
+ * nothing else touched.  Leaves alone what zigz_dev_mle_eval_batch leaves alone. */
+#define ZIGZ_FACTOR_TABLE 0
+#define ZIGZ_FACTOR_EQ 1
+zigz_status zigz_dev_sumcheck_verify_product_batch(zigz_ctx *ctx, size_t k, const unsigned *degrees,
+                                                   const uint32_t *const *d_factors, const uint8_t *factor_kinds,
+                                                   const uint64_t *eq_points, const size_t *ns, const uint64_t *claimed_sums,
+                                                   const uint64_t *rounds, const uint64_t *points, const uint64_t *factor_evals,
+                                                   const uint64_t *final_evals, uint32_t flags, uint8_t *verdicts,
+                                                   uint64_t *expected_evals, uint64_t *oracle_evals, size_t *n_rejected,
+                                                   size_t *bad_index);
+/* host tables (canonical u64, ZIGZ_ERR_NOT_CANONICAL with the proof's index otherwise), narrowed and uploaded in one copy */
+zigz_status zigz_sumcheck_verify_product_batch(zigz_ctx *ctx, size_t k, const unsigned *degrees, const uint64_t *const *factors,
+                                               const uint8_t *factor_kinds, const uint64_t *eq_points, const size_t *ns,
+                                               const uint64_t *claimed_sums, const uint64_t *rounds, const uint64_t *points,
+                                               const uint64_t *factor_evals, const uint64_t *final_evals, uint32_t flags,
+                                               uint8_t *verdicts, uint64_t *expected_evals, uint64_t *oracle_evals,
+                                               size_t *n_rejected, size_t *bad_index);
+
 /* ---------------------------------------------------------------- host SHA3 sponge / transcript
  * FiatShamirTranscript   src/core/hash.zig:255-324 (sequential by construction: stays on the host) */
 zigz_transcript *zigz_transcript_new(void);

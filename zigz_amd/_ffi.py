@@ -164,6 +164,12 @@ SIGNATURES = {
                                                           u64p, u64p, szp]),
     "zigz_sumcheck_prove_product_batch": (C.c_int32, [vp, C.c_size_t, C.POINTER(C.c_uint), C.POINTER(u64p), szp, u64p, u64p, u64p, u64p,
                                                       u64p, u64p, szp]),
+    "zigz_dev_eq_table_batch": (C.c_int32, [vp, C.c_size_t, szp, u64p, C.POINTER(vp), szp]),
+    "zigz_eq_table_batch": (C.c_int32, [vp, C.c_size_t, szp, u64p, C.POINTER(u64p), szp]),
+    "zigz_dev_sumcheck_verify_product_batch": (C.c_int32, [vp, C.c_size_t, C.POINTER(C.c_uint), C.POINTER(vp), u8p, u64p, szp, u64p, u64p,
+                                                           u64p, u64p, u64p, C.c_uint32, u8p, u64p, u64p, szp, szp]),
+    "zigz_sumcheck_verify_product_batch": (C.c_int32, [vp, C.c_size_t, C.POINTER(C.c_uint), C.POINTER(u64p), u8p, u64p, szp, u64p, u64p,
+                                                       u64p, u64p, u64p, C.c_uint32, u8p, u64p, u64p, szp, szp]),
     "zigz_sumcheck_radix_run_batch": (C.c_int32, [vp, RB_BLOCK_SUMS_FN, RB_FOLD_FN, RB_READ_TAIL_FN, C.c_size_t, szp, u64p, u64p, u64p,
                                                   u64p]),
     "zigz_dev_sumcheck_prove_rccl": (C.c_int32, [vp, vp, C.c_size_t, vp, u64p, u64p, u64p]),

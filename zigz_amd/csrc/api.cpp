@@ -148,6 +148,24 @@ zigz_status pinned(zigz_ctx *ctx, size_t bytes, uint8_t **out) {
     return ZIGZ_OK;
 }
 
+// Pinned staging for the descriptors of an entry that returns while its upload may still be in flight (zigz_dev_merkle_open_many,
+// zigz_dev_eq_table_batch): a region of its own, handed out only once the last such upload has left it.  The caller records
+// ctx->ev_open right behind its copy.
+zigz_status upload_region(zigz_ctx *ctx, size_t bytes, uint8_t **out) {
+    if (!ctx->ev_open) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_open, hipEventDisableTiming));
+    else HIPCHK(ctx, hipEventSynchronize(ctx->ev_open));
+    if (ctx->h_open_bytes < bytes) {
+        if (ctx->h_open) (void)hipHostFree(ctx->h_open);
+        ctx->h_open = nullptr;
+        ctx->h_open_bytes = 0;
+        const size_t want = align256(bytes + bytes / 8);
+        HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_open, want, hipHostMallocDefault));
+        ctx->h_open_bytes = want;
+    }
+    *out = ctx->h_open;
+    return ZIGZ_OK;
+}
+
 extern "C" zigz_status zigz_device_set_blocking_sync(int device, int on) {
     int n = 0;
     if (zigz_device_count(&n) != ZIGZ_OK || device < 0 || device >= n) return ZIGZ_ERR_NO_DEVICE;

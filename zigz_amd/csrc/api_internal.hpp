@@ -29,7 +29,7 @@
 using namespace zk;
 
 // ------------------------------------------------------------------ context
-enum { WS_IN64 = 0, WS_IN32, WS_OUT32, WS_OUT64, WS_SCRATCH, WS_TREE, WS_FOLD, WS_MISC, WS_COLS, WS_LASSO, WS_DEDUP, WS_WITNESS, WS_RUNS, WS_RUNMETA, WS_CONS, WS_CONSMETA, WS_BATCH, WS_SCBATCH, WS_SCBATCH_IN, WS_VERIFY, WS_OPEN, WS_MLEBATCH, WS_MLEBATCH_PART, WS_MLEBATCH_IN, WS_PRODUCT, WS_PRODUCT_WORK, WS_PRODUCT_IN, WS_SLOTS };
+enum { WS_IN64 = 0, WS_IN32, WS_OUT32, WS_OUT64, WS_SCRATCH, WS_TREE, WS_FOLD, WS_MISC, WS_COLS, WS_LASSO, WS_DEDUP, WS_WITNESS, WS_RUNS, WS_RUNMETA, WS_CONS, WS_CONSMETA, WS_BATCH, WS_SCBATCH, WS_SCBATCH_IN, WS_VERIFY, WS_OPEN, WS_MLEBATCH, WS_MLEBATCH_PART, WS_MLEBATCH_IN, WS_PRODUCT, WS_PRODUCT_WORK, WS_PRODUCT_IN, WS_EQ, WS_EQ_OUT, WS_SLOTS };
 
 constexpr int KEV_MAX = 72;
 struct zigz_ctx {
@@ -95,8 +95,9 @@ struct zigz_ctx {
     size_t h_batch_bytes;
     hipEvent_t ev_verify[2];  // the batched verify's host form: the upload from each half of its pinned staging (created on first use)
     int verify_pause;         // option "verify_pause": 0 = by launch size, 1 = always, 2 = never (A/B)
-    uint8_t *h_open;          // pinned descriptor staging of zigz_dev_merkle_open_many, which returns while its upload may still
-    size_t h_open_bytes;      // be in flight: its own region, not reused before ev_open (recorded behind the upload) has passed
+    uint8_t *h_open;          // pinned descriptor staging of zigz_dev_merkle_open_many and zigz_dev_eq_table_batch, which return while
+    size_t h_open_bytes;      // their upload may still be in flight: its own region, not reused before ev_open (recorded behind
+                              // the upload) has passed (upload_region)
     hipEvent_t ev_open;
 };
 static const size_t FLUSH_BYTES = (size_t)1 << 30;
@@ -154,6 +155,7 @@ bool spin_wait(const unsigned long long *flag, unsigned long long seq);
 DoneFlag done_flag(zigz_ctx *ctx, int which);
 zigz_status wait_published(zigz_ctx *ctx, const DoneFlag &done);
 zigz_status pinned(zigz_ctx *ctx, size_t bytes, uint8_t **out);
+zigz_status upload_region(zigz_ctx *ctx, size_t bytes, uint8_t **out);
 zigz_status log_launch(zigz_ctx *ctx, int cls, uint64_t perms, hipEvent_t start, hipEvent_t stop, hipEvent_t first, double *dur_us);
 zigz_status upload_u64(zigz_ctx *ctx, const uint64_t *h_in, size_t n, uint32_t *d_out, bool reduce);
 zigz_status download_u64(zigz_ctx *ctx, const uint32_t *d_in, size_t n, uint64_t *h_out);

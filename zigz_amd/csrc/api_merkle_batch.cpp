@@ -407,25 +407,17 @@ zigz_status open_many_dev(zigz_ctx *ctx, const zigz_merkle_batch *b, const uint3
                           const std::vector<uint64_t> &off, size_t k, uint8_t *d_siblings, uint8_t *d_dirs, uint64_t *d_leaf_values,
                           uint8_t *d_roots) {
     const size_t tabs_bytes = align256(b->k * sizeof(MOpenTree)), up_bytes = tabs_bytes + k * sizeof(mo::Desc);
-    if (!ctx->ev_open) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_open, hipEventDisableTiming));
-    else HIPCHK(ctx, hipEventSynchronize(ctx->ev_open));
-    if (ctx->h_open_bytes < up_bytes) {
-        if (ctx->h_open) (void)hipHostFree(ctx->h_open);
-        ctx->h_open = nullptr;
-        ctx->h_open_bytes = 0;
-        const size_t want = align256(up_bytes + up_bytes / 8);
-        HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_open, want, hipHostMallocDefault));
-        ctx->h_open_bytes = want;
-    }
+    uint8_t *h_up;
+    CHK(upload_region(ctx, up_bytes, &h_up));
     void *ws;
     CHK(ws_get(ctx, WS_OPEN, up_bytes, &ws));
     mo::Chunk c{};
     c.hi = k;
     bool zero_height = false;
     for (size_t j = 0; j < k && !zero_height; j++) zero_height = off[j + 1] == off[j];
-    fill_trees(b, (MOpenTree *)ctx->h_open);
-    fill_descs(c, trees, indices, off, (mo::Desc *)(ctx->h_open + tabs_bytes));
-    HIPCHK(ctx, hipMemcpyAsync(ws, ctx->h_open, up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    fill_trees(b, (MOpenTree *)h_up);
+    fill_descs(c, trees, indices, off, (mo::Desc *)(h_up + tabs_bytes));
+    HIPCHK(ctx, hipMemcpyAsync(ws, h_up, up_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipEventRecord(ctx->ev_open, ctx->stream));
     const MOpenOut o{d_siblings, d_dirs, d_leaf_values, d_roots};
     launch_mbatch_open_many((const MOpenTree *)ws, (const mo::Desc *)((uint8_t *)ws + tabs_bytes), (unsigned)k, (unsigned)off[k],

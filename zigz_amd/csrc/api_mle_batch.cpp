@@ -1,5 +1,6 @@
 // C ABI of libzigz_hip.so, part 8: batched MLE evaluation over free-standing tables and batched sumcheck verification on top of
-// it.
+// it; batched eq tables and the verification of product proofs, whose table factors go through the same eval
+// launch.
 //
 // Schedule of one call: the host writes the k descriptors and the 2 v factors of every point (1 - r and r, Montgomery form)
 // into pinned memory and queues ONE copy of them, ONE launch that evaluates all k pairs (mle_batch.hip: exact u64 sums, one
@@ -8,8 +9,12 @@
 // queue the same copy and two launches over the proofs' final points, replay the k transcripts on the host's threads while the GPU
 // evaluates (the evaluation point comes from the proof, not from the transcript, so neither waits for the other), and combine
 // the two after the hand-off.  The argument checks and the replay are plain host code: sumcheck_verify_host.hpp.
+//
+// The product verifier is the same schedule over one (table, point) pair per TABLE factor of every proof; a factor eq(tau, .) is
+// v multiplications on the host next to the replay and never a table.  The eq tables are one copy (descriptors and factor pairs)
+// and one launch (eq_batch.hip) that the device form leaves queued.  Checks, replay, eq_at, verdict: product_verify_host.hpp.
 #include "api_internal.hpp"
-#include "sumcheck_verify_host.hpp"
+#include "product_verify_host.hpp"
 
 using namespace zk;
 
@@ -143,6 +148,162 @@ zigz_status verify_batch(zigz_ctx *ctx, const uint32_t *const *d_tables, const u
     ZIGZ_NOTHROW_END(ctx)
 }
 
+// ---- product proofs: the oracles are the proofs' factors, a table (one pair of the eval launch) or eq(tau, .) (host, closed form)
+zigz_status verify_product_batch(zigz_ctx *ctx, const pv::VerifyArgs &a, bool host_tables, uint8_t *verdicts,
+                                 uint64_t *expected_evals, uint64_t *oracle_evals, size_t *n_rejected, size_t *bad_index) {
+    ZIGZ_NOTHROW_BEGIN
+    const size_t k = a.k;
+    const bool reversed = (a.flags & ZIGZ_SUMCHECK_VERIFY_POINT_REVERSED) != 0;
+    // per proof: its first factor, variable, round word and tau word; per table factor: one pair of the eval launch
+    std::vector<size_t> foff(k + 1, 0), voff(k + 1, 0), roff(k + 1, 0), eoff(k + 1, 0);
+    std::vector<const void *> tabs;
+    std::vector<size_t> pair_ns, owner, pair_of;
+    std::vector<uint64_t> pair_points;
+    for (size_t i = 0; i < k; i++) {
+        const unsigned d = a.degrees[i];
+        const size_t v = log2_floor(a.ns[i]);
+        size_t neq = 0;
+        for (unsigned j = 0; j < d; j++) {
+            if (pv::kind_of(a, foff[i] + j) == pv::KIND_EQ) {
+                neq++;
+                pair_of.push_back((size_t)-1);
+                continue;
+            }
+            pair_of.push_back(tabs.size());
+            tabs.push_back(a.factors[foff[i] + j]);
+            pair_ns.push_back(a.ns[i]);
+            owner.push_back(i);
+            pair_points.insert(pair_points.end(), a.points + voff[i], a.points + voff[i] + v);
+        }
+        foff[i + 1] = foff[i] + d;
+        voff[i + 1] = voff[i] + v;
+        roff[i + 1] = roff[i] + (size_t)(d + 1) * v;
+        eoff[i + 1] = eoff[i] + neq * v;
+    }
+    const size_t m = tabs.size();
+    Layout L;
+    CHK(plan(pair_ns.data(), m, host_tables, L));
+    DoneFlag done;
+    uint8_t *pin = nullptr;
+    if (m) {  // (a call without a table factor launches nothing)
+        CHK(pinned(ctx, L.bytes, &pin));
+        std::vector<const uint32_t *> d;
+        if (host_tables) {
+            CHK(stage_host_tables(ctx, (const uint64_t *const *)tabs.data(), pair_ns.data(), m, L.at, (uint32_t *)(pin + L.tab_off),
+                                  WS_MLEBATCH_IN, owner.data(), d, bad_index));
+        } else {
+            d.assign((const uint32_t *const *)tabs.data(), (const uint32_t *const *)tabs.data() + m);
+        }
+        CHK(eval_queue(ctx, L, pin, d.data(), pair_ns.data(), pair_points.data(), reversed, &done));
+    }
+    // the k replays and the eq factors, underneath the evaluation
+    std::vector<sv::Replay> rep(k);
+    std::vector<uint64_t> ev(foff[k], 0);
+    parallel_for(k, [&](size_t i) {
+        const size_t v = voff[i + 1] - voff[i];
+        rep[i] = pv::replay_rounds(a.claimed_sums[i], a.rounds + roff[i], v, a.degrees[i]);
+        const uint64_t *tau = a.eq_points ? a.eq_points + eoff[i] : nullptr;
+        for (size_t f = foff[i]; f < foff[i + 1]; f++)
+            if (pair_of[f] == (size_t)-1) {
+                ev[f] = pv::eq_at(tau, a.points + voff[i], v, reversed);
+                tau += v;
+            }
+    });
+    if (m) CHK(wait_published(ctx, done));
+    const uint64_t *pairs = (const uint64_t *)pin;
+    size_t rejected = 0;
+    for (size_t i = 0; i < k; i++) {
+        for (size_t f = foff[i]; f < foff[i + 1]; f++)
+            if (pair_of[f] != (size_t)-1) ev[f] = pairs[pair_of[f]];
+        const uint8_t ok = pv::verdict(rep[i], ev.data() + foff[i], a.degrees[i], a.final_evals[i],
+                                       a.factor_evals ? a.factor_evals + foff[i] : nullptr);
+        rejected += !ok;
+        if (verdicts) verdicts[i] = ok;
+        if (expected_evals) expected_evals[i] = rep[i].expected;
+    }
+    if (oracle_evals) memcpy(oracle_evals, ev.data(), foff[k] * 8);
+    *n_rejected = rejected;
+    return ZIGZ_OK;
+    ZIGZ_NOTHROW_END(ctx)
+}
+
+// ---- eq tables
+constexpr size_t EQ_DOWNLOAD_BYTES = (size_t)32 << 20;  // pinned staging per chunk of the host form's download
+
+inline size_t eq_chunks(const size_t *ns, size_t k) {
+    size_t nwg = 0;
+    for (size_t i = 0; i < k; i++) nwg += (ns[i] + MLE_BATCH_CHUNK - 1) / MLE_BATCH_CHUNK;
+    return nwg;
+}
+
+// One copy (descriptors | factor pairs, from the staging region that outlives the call) and one launch, left queued on the
+// context's stream.  ns[i] are powers of two <= 2^32, d_out[i] 16-byte aligned, the tables together at most MLE_BATCH_MAX_WGS
+// chunks (checked by the callers).
+zigz_status eq_queue(zigz_ctx *ctx, size_t k, const size_t *ns, const uint64_t *points, uint32_t *const *d_out) {
+    size_t tot_v = 0;
+    for (size_t i = 0; i < k; i++) tot_v += log2_floor(ns[i]);
+    const size_t nwg = eq_chunks(ns, k);
+    const size_t f_off = align256(k * sizeof(EqBatchTab)), bytes = f_off + align256(2 * tot_v * 4 + 4);
+    uint8_t *h;
+    void *d_stage;
+    CHK(upload_region(ctx, bytes, &h));
+    CHK(ws_get(ctx, WS_EQ, bytes, &d_stage));
+    EqBatchTab *tab = (EqBatchTab *)h;
+    uint32_t *f = (uint32_t *)(h + f_off);
+    size_t off = 0, wg = 0;
+    for (size_t i = 0; i < k; i++) {
+        const unsigned nv = log2_floor(ns[i]);
+        EqBatchTab t{};
+        t.out = d_out[i];
+        t.n = ns[i];
+        t.nv = nv;
+        t.first_wg = (uint32_t)wg;
+        t.f_off = (uint32_t)(2 * off);
+        tab[i] = t;
+        for (unsigned v = 0; v < nv; v++) {
+            f[2 * (off + v)] = host_to_mont(f_sub(1, points[off + v]));
+            f[2 * (off + v) + 1] = host_to_mont(points[off + v]);
+        }
+        off += nv;
+        wg += (ns[i] + MLE_BATCH_CHUNK - 1) / MLE_BATCH_CHUNK;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(d_stage, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev_open, ctx->stream));
+    launch_eq_batch_expand((const EqBatchTab *)d_stage, (unsigned)k, (unsigned)nwg, (const uint32_t *)((const uint8_t *)d_stage + f_off),
+                           ctx->stream);
+    HIPCHK(ctx, hipGetLastError());
+    return ZIGZ_OK;
+}
+
+// Host form: the tables are built into a workspace, one behind the other (every table 16-byte aligned), and come back through
+// pinned memory in chunks of at most EQ_DOWNLOAD_BYTES, widened to u64 on the way into the caller's arrays.
+zigz_status eq_host(zigz_ctx *ctx, size_t k, const size_t *ns, const uint64_t *points, uint64_t *const *out) {
+    ZIGZ_NOTHROW_BEGIN
+    const std::vector<size_t> at = packed_offsets(ns, k);
+    void *d_tabs;
+    CHK(ws_get(ctx, WS_EQ_OUT, at[k] * 4, &d_tabs));
+    std::vector<uint32_t *> d(k);
+    for (size_t i = 0; i < k; i++) d[i] = (uint32_t *)d_tabs + at[i];
+    CHK(eq_queue(ctx, k, ns, points, d.data()));
+    const size_t chunk = EQ_DOWNLOAD_BYTES / 4;
+    uint8_t *pin;
+    CHK(pinned(ctx, (at[k] < chunk ? at[k] : chunk) * 4, &pin));
+    const uint32_t *h = (const uint32_t *)pin;
+    size_t first = 0;  // the first table that reaches past the words already taken
+    for (size_t lo = 0; lo < at[k]; lo += chunk) {
+        const size_t hi = lo + chunk < at[k] ? lo + chunk : at[k];
+        HIPCHK(ctx, hipMemcpyAsync(pin, (const uint32_t *)d_tabs + lo, (hi - lo) * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        while (first < k && at[first] + ns[first] <= lo) first++;
+        for (size_t i = first; i < k && at[i] < hi; i++) {
+            const size_t a = at[i] > lo ? at[i] : lo, b = at[i] + ns[i] < hi ? at[i] + ns[i] : hi;
+            for (size_t x = a; x < b; x++) out[i][x - at[i]] = h[x - lo];
+        }
+    }
+    return ZIGZ_OK;
+    ZIGZ_NOTHROW_END(ctx)
+}
+
 }  // namespace
 
 extern "C" zigz_status zigz_dev_mle_eval_batch(zigz_ctx *ctx, const uint32_t *const *d_tables, const size_t *ns, size_t k,
@@ -199,4 +360,65 @@ extern "C" zigz_status zigz_sumcheck_verify_batch(zigz_ctx *ctx, const uint64_t 
     }
     return verify_batch(ctx, nullptr, tables, ns, k, claimed_sums, rounds, points, final_evals, flags, verdicts, expected_evals,
                         oracle_evals, n_rejected, bad_index);
+}
+
+extern "C" zigz_status zigz_dev_sumcheck_verify_product_batch(zigz_ctx *ctx, size_t k, const unsigned *degrees,
+                                                              const uint32_t *const *d_factors, const uint8_t *factor_kinds,
+                                                              const uint64_t *eq_points, const size_t *ns, const uint64_t *claimed_sums,
+                                                              const uint64_t *rounds, const uint64_t *points,
+                                                              const uint64_t *factor_evals, const uint64_t *final_evals, uint32_t flags,
+                                                              uint8_t *verdicts, uint64_t *expected_evals, uint64_t *oracle_evals,
+                                                              size_t *n_rejected, size_t *bad_index) {
+    ZIGZ_ENTER(ctx);
+    if (!ctx) return ZIGZ_ERR_INVALID_ARGUMENT;
+    const pv::VerifyArgs a{k, degrees, (const void *const *)d_factors, factor_kinds, eq_points, ns, claimed_sums, rounds, points,
+                           factor_evals, final_evals, flags, n_rejected};
+    CHK(pv::check_verify_product_batch(a, true, false, bad_index));
+    if (k == 0) {
+        *n_rejected = 0;
+        return ZIGZ_OK;
+    }
+    return verify_product_batch(ctx, a, false, verdicts, expected_evals, oracle_evals, n_rejected, bad_index);
+}
+
+extern "C" zigz_status zigz_sumcheck_verify_product_batch(zigz_ctx *ctx, size_t k, const unsigned *degrees,
+                                                          const uint64_t *const *factors, const uint8_t *factor_kinds,
+                                                          const uint64_t *eq_points, const size_t *ns, const uint64_t *claimed_sums,
+                                                          const uint64_t *rounds, const uint64_t *points, const uint64_t *factor_evals,
+                                                          const uint64_t *final_evals, uint32_t flags, uint8_t *verdicts,
+                                                          uint64_t *expected_evals, uint64_t *oracle_evals, size_t *n_rejected,
+                                                          size_t *bad_index) {
+    ZIGZ_ENTER(ctx);
+    if (!ctx) return ZIGZ_ERR_INVALID_ARGUMENT;
+    const pv::VerifyArgs a{k, degrees, (const void *const *)factors, factor_kinds, eq_points, ns, claimed_sums, rounds, points,
+                           factor_evals, final_evals, flags, n_rejected};
+    bool value = false;
+    const zigz_status st = pv::check_verify_product_batch_host(a, bad_index, &value);
+    if (value) set_err(ctx, "%s", NOT_CANONICAL_TEXT);
+    CHK(st);
+    if (k == 0) {
+        *n_rejected = 0;
+        return ZIGZ_OK;
+    }
+    return verify_product_batch(ctx, a, true, verdicts, expected_evals, oracle_evals, n_rejected, bad_index);
+}
+
+extern "C" zigz_status zigz_dev_eq_table_batch(zigz_ctx *ctx, size_t k, const size_t *ns, const uint64_t *points,
+                                               uint32_t *const *d_out, size_t *bad_index) {
+    ZIGZ_ENTER(ctx);
+    if (!ctx) return ZIGZ_ERR_INVALID_ARGUMENT;
+    if (k == 0) return ZIGZ_OK;
+    CHK(pv::check_eq_table_batch(k, ns, points, (const void *const *)d_out, true, bad_index));
+    if (eq_chunks(ns, k) > MLE_BATCH_MAX_WGS) return ZIGZ_ERR_INVALID_ARGUMENT;  // one launch: fewer than 2^32 threads in its grid
+    return eq_queue(ctx, k, ns, points, d_out);
+}
+
+extern "C" zigz_status zigz_eq_table_batch(zigz_ctx *ctx, size_t k, const size_t *ns, const uint64_t *points, uint64_t *const *out,
+                                           size_t *bad_index) {
+    ZIGZ_ENTER(ctx);
+    if (!ctx) return ZIGZ_ERR_INVALID_ARGUMENT;
+    if (k == 0) return ZIGZ_OK;
+    CHK(pv::check_eq_table_batch(k, ns, points, (const void *const *)out, false, bad_index));
+    if (eq_chunks(ns, k) > MLE_BATCH_MAX_WGS) return ZIGZ_ERR_INVALID_ARGUMENT;  // one launch: fewer than 2^32 threads in its grid
+    return eq_host(ctx, k, ns, points, out);
 }

@@ -569,6 +569,18 @@ void launch_mle_batch_eval(const MleBatchTab *d_tabs, unsigned nt, unsigned nwg,
 void launch_mle_batch_finish(const MleBatchTab *d_tabs, unsigned nt, const unsigned long long *d_part, uint64_t *out, hipStream_t s,
                              DoneFlag done);
 
+// ---- batched eq tables (eq_batch.hip): E[x] = prod_v f_v[bit v of x] for k (length, point) pairs in one launch, in the chunk
+// layout of the batched eval (a workgroup owns MLE_BATCH_CHUNK consecutive words of one table; MLE_BATCH_MAX_WGS per launch)
+struct EqBatchTab {  // one table; its workgroups are [first_wg, first_wg of table j + 1)
+    uint32_t *out;   // 2^nv packed canonical words, 16-byte aligned; nothing behind them is written
+    uint64_t n;
+    uint32_t nv;
+    uint32_t first_wg;
+    uint32_t f_off;  // the table's 2 nv factors in the factor array, as MleBatchTab's
+    uint32_t reserved;
+};
+void launch_eq_batch_expand(const EqBatchTab *d_tabs, unsigned nt, unsigned nwg, const uint32_t *d_f, hipStream_t s);
+
 // ---- batched product sumcheck (sumcheck_product.hip): the round polynomials of sum_x prod_{j<d} f_j(x), d <= 3, for k
 // independent instances, one data pass per round.  A workgroup owns one chunk of PRODUCT_CHUNK consecutive elements of one
 // instance's current tables (a smaller table is one partial chunk); product_host.hpp holds the host side.

@@ -25,33 +25,11 @@
 // (zigz_commit_open_batch), into device words that the path launch behind it reads, signalling nothing.  With
 // n <= 2^MLE_BATCH_MAX_LOG2_N a pair's sum stays below 2^31 * n <= 2^63 and cannot wrap.  Every partial is written by every
 // launch, so nothing has to be zeroed between calls.
-#include "kernels.hpp"
-
-#include "field.hpp"
-#include "tree_dev.hpp"
+#include "mle_batch_dev.hpp"  // the chunk's weights U, A, B, H (shared with k_eq_batch_expand, eq_batch.hip)
 
 namespace zk {
 
-namespace {
-
-constexpr int ME_LOADS = MLE_BATCH_CHUNK / (4 * TPB);  // 16-byte loads per lane
-constexpr unsigned ME_LANE_BIT = 2, ME_LOOP_BIT = 10, ME_HI_BIT = 13;  // first index bit of the thread, the load, the workgroup
-static_assert(ME_LOADS == 8 && MLE_BATCH_CHUNK == 1u << ME_HI_BIT, "index bits: 2 component, 8 thread, 3 load, the rest workgroup");
-static_assert(TPB == 256, "A and B cover the thread's 8 index bits, wave 1 the high variables, four wave sums per workgroup");
 static_assert(31 + MLE_BATCH_MAX_LOG2_N < 64, "a pair's exact u64 sum: fewer than n terms below p < 2^31");
-static_assert(ME_HI_BIT + 64 > MLE_BATCH_MAX_LOG2_N, "one wave holds a factor per high variable");
-
-// prod_{i < cnt} f_{v0 + i}[bit i of bits], Montgomery form; a variable the table does not have contributes (1, 0)
-__device__ __forceinline__ uint32_t me_eq(const uint32_t *__restrict__ f, unsigned nv, unsigned v0, unsigned cnt, unsigned bits) {
-    uint32_t w = R_MOD_P;
-    for (unsigned i = 0; i < cnt; i++) {
-        const unsigned v = v0 + i, b = (bits >> i) & 1;
-        w = mont_mul(w, v < nv ? f[2 * v + b] : (b ? 0u : R_MOD_P));
-    }
-    return w;
-}
-
-}  // namespace
 
 __global__ __launch_bounds__(TPB) void k_mle_batch_eval(const MleBatchTab *__restrict__ tabs, unsigned nt,
                                                         const uint32_t *__restrict__ factors, unsigned long long *__restrict__ part) {
@@ -63,21 +41,8 @@ __global__ __launch_bounds__(TPB) void k_mle_batch_eval(const MleBatchTab *__res
     const uint32_t *f = factors + d.f_off;
     const unsigned t = threadIdx.x, nv = d.nv;
     const size_t base = (size_t)(blockIdx.x - d.first_wg) * MLE_BATCH_CHUNK;
-    if (t < 32) {
-        s_u[t] = mont_mul(me_eq(f, nv, 0, ME_LANE_BIT, t & 3), me_eq(f, nv, ME_LOOP_BIT, ME_HI_BIT - ME_LOOP_BIT, t >> 2));
-    } else if (t < 48) {
-        s_a[t - 32] = me_eq(f, nv, ME_LANE_BIT, 4, t - 32);
-    } else if (t < 64) {
-        s_b[t - 48] = me_eq(f, nv, ME_LANE_BIT + 4, 4, t - 48);
-    } else if (t < 128) {  // wave 1: H, the factors of the workgroup's own index bits multiplied across the lanes
-        const unsigned v = ME_HI_BIT + (t - 64);
-        uint32_t w = v < nv ? f[2 * v + (unsigned)((base >> v) & 1)] : R_MOD_P;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) w = mont_mul(w, __shfl_down(w, off, 64));
-        // one more factor R: the lane's sum arrives divided by R (monty_reduce below)
-        if (t == 64) s_hi = mont_mul(w, R2_MOD_P);
-    }
-    __syncthreads();
+    // one more factor R on H: the lane's sum arrives divided by R (monty_reduce below)
+    me_chunk_weights(f, nv, base, t, R2_MOD_P, s_u, s_a, s_b, &s_hi);
     unsigned long long lo = 0, hi = 0;
     if (d.n >= 4) {  // uniform over the workgroup
         const uint4 *p = reinterpret_cast<const uint4 *>(d.vals);

@@ -508,6 +508,80 @@ class Context:
         ptrs = (vp * max(len(flat), 1))(*flat)
         return self._product_batch(lib.zigz_dev_sumcheck_prove_product_batch, ptrs, [len(inst) for inst in d_instances], ns, challenges)
 
+    # ---- batched eq tables and the verification of product proofs (a zero-check end to end: DESIGN.md s7h)
+    def eq_table_batch(self, ns, points):
+        """zigz_eq_table_batch: for every i the table E[x] = prod_j (bit j of x ? tau_j : 1 - tau_j) of ns[i] = 2^v canonical
+        words, tau = points[i] (v coordinates, tau[0] with the LSB of x).  Returns the list of np.uint64 arrays."""
+        k = len(ns)
+        nsa = (C.c_size_t * max(k, 1))(*[int(n) for n in ns])
+        q, qp = self._cat_u64(points)
+        outs = [_out_u64(n) for n in ns]
+        ptrs = (u64p * max(k, 1))(*[p for _, p in outs])
+        bad = C.c_size_t(0)
+        self.check_batch(lib.zigz_eq_table_batch(self.h, k, nsa, qp, ptrs, C.byref(bad)), bad)
+        return [o[:int(n)] for (o, _), n in zip(outs, ns)]
+
+    def dev_eq_table_batch(self, d_out, ns, points):
+        """zigz_dev_eq_table_batch into device memory (addresses, 16-byte aligned, ns[i] u32 words each): queued on the context's
+        stream, not waited for."""
+        k = len(ns)
+        nsa = (C.c_size_t * max(k, 1))(*[int(n) for n in ns])
+        ptrs = (vp * max(k, 1))(*[int(d) for d in d_out])
+        q, qp = self._cat_u64(points)
+        bad = C.c_size_t(0)
+        self.check_batch(lib.zigz_dev_eq_table_batch(self.h, k, nsa, qp, ptrs, C.byref(bad)), bad)
+
+    def _verify_product_batch(self, fn, ptrs, degrees, kinds, taus, ns, proofs, flags, check_factor_evals):
+        k = len(ns)
+        dg = (C.c_uint * max(k, 1))(*[int(d) for d in degrees])
+        nsa = (C.c_size_t * max(k, 1))(*[int(n) for n in ns])
+        kp = None
+        if kinds is not None:
+            kn = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint8).reshape(-1) for x in kinds] + [np.zeros(1, np.uint8)]))
+            kp = kn.ctypes.data_as(u8p)
+        tp = None
+        if taus is not None:
+            tq, tp = self._cat_u64(taus)
+        cs, csp = self._cat_u64([[int(p[0]) for p in proofs]])
+        r, rp = self._cat_u64([p[1] for p in proofs])
+        q, qp = self._cat_u64([p[2] for p in proofs])
+        fv, fvp = self._cat_u64([p[3] for p in proofs])
+        fe, fep = self._cat_u64([[int(p[4]) for p in proofs]])
+        nf = sum(int(d) for d in degrees)
+        verd, vdp = _out_u8(k)
+        exp, ep = _out_u64(k)
+        orc, op = _out_u64(nf)
+        rej, bad = C.c_size_t(0), C.c_size_t(0)
+        self.check_batch(fn(self.h, k, dg, ptrs, kp, tp, nsa, csp, rp, qp, fvp if check_factor_evals else None, fep, int(flags), vdp, ep,
+                            op, C.byref(rej), C.byref(bad)), bad)
+        oracle, o = [], 0
+        for d in degrees:
+            oracle.append([int(x) for x in orc[o: o + int(d)]])
+            o += int(d)
+        return verd[:k].copy(), [int(x) for x in exp[:k]], oracle, rej.value
+
+    def sumcheck_verify_product_batch(self, instances, proofs, flags=0, taus=None, check_factor_evals=True):
+        """zigz_sumcheck_verify_product_batch: proofs[i] = (claimed_sum, rounds, point, factor_evals, final_eval) as
+        sumcheck_prove_product_batch returns it, instances[i] the list of its 1..3 factors -- a table, or None for eq(tau, .),
+        whose tau is the next entry of `taus`.  flags as sumcheck_verify_batch's.  check_factor_evals=False passes
+        factor_evals = NULL.  Returns (verdicts np.uint8, expected_evals, oracle_evals [d per proof], n_rejected)."""
+        arrs = [(None, None) if t is None else _u64(t) for inst in instances for t in inst]
+        ptrs = (u64p * max(len(arrs), 1))(*[p for _, p in arrs])
+        kinds = [[1 if t is None else 0 for t in inst] for inst in instances]
+        ns = [1 << len(p[2]) if all(t is None for t in inst) else len(next(t for t in inst if t is not None))
+              for inst, p in zip(instances, proofs)]
+        return self._verify_product_batch(lib.zigz_sumcheck_verify_product_batch, ptrs, [len(inst) for inst in instances], kinds, taus,
+                                          ns, proofs, flags, check_factor_evals)
+
+    def dev_sumcheck_verify_product_batch(self, d_instances, ns, proofs, flags=0, taus=None, check_factor_evals=True):
+        """zigz_dev_sumcheck_verify_product_batch: d_instances[i] lists proof i's factors as device addresses (packed u32
+        canonical, 16-byte aligned, ns[i] values), None for eq(tau, .)."""
+        flat = [d for inst in d_instances for d in inst]
+        ptrs = (vp * max(len(flat), 1))(*[None if d is None else int(d) for d in flat])
+        kinds = [[1 if d is None else 0 for d in inst] for inst in d_instances]
+        return self._verify_product_batch(lib.zigz_dev_sumcheck_verify_product_batch, ptrs, [len(inst) for inst in d_instances], kinds,
+                                          taus, ns, proofs, flags, check_factor_evals)
+
     def _merkle_batch_out(self, rc, bad, k, roots, heights, handle, ns, keep):
         self.check_batch(rc, bad)
         res = [(roots[32 * i: 32 * (i + 1)].tobytes(), int(heights[i])) for i in range(k)]
