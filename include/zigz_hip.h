@@ -700,6 +700,82 @@ zigz_status zigz_sumcheck_verify_product_batch(zigz_ctx *ctx, size_t k, const un
                                                uint8_t *verdicts, uint64_t *expected_evals, uint64_t *oracle_evals,
                                                size_t *n_rejected, size_t *bad_index);
 
+/* k independent sumchecks of a SUM OF PRODUCTS of multilinear tables in shared launches (a constraint system under one
+ * transcript): instance i has a POOL of M_i = n_tables[i] tables (1..ZIGZ_SOP_MAX_TABLES) of ns[i] = 2^v_i elements each and
+ * T_i = n_terms[i] TERMS (1..ZIGZ_SOP_MAX_TERMS); term t is a coefficient alpha_t (canonical, 0 allowed) times a product of
+ * d_t in 1..ZIGZ_PRODUCT_MAX_DEGREE pool tables named by index -- an index may repeat within a term and across terms, and a pool
+ * table that no term names is bound and reported like the others.  The instance proves
+ *   S_i = sum_{x in {0,1}^v_i} sum_{t < T_i} alpha_t prod_{j < d_t} pool[idx(t, j)](x)
+ * with round polynomials of D_i + 1 coefficients c_0..c_D, D_i = max_t d_t (C(x) = sum_j alpha_j constraint_j(x),
+ * src/prover/prover.zig:241-248).  Everything else is zigz_dev_sumcheck_prove_product_batch's: partialEval's MSB-first bind, a
+ * fresh transcript per instance that absorbs c_0..c_D and then draws, fixed_challenges != NULL as the proveInteractive form, the
+ * instances longer than 1024 on the device and the tails on the host after one hand-off.  With eq(tau, .) from
+ * zigz_dev_eq_table_batch as a pool table that every term names this is the zero-check sum_x eq(tau, x) C(x) = 0 of a constraint
+ * system C: one transcript, one point, every distinct table bound once per round.
+ * Layout, everything concatenated in instance order: d_tables (sum M_i pointers), term_degrees and term_coeffs (sum T_i), term_tables
+ * (one byte per factor, term by term: sum of all d_t).  Outputs: claimed_sums[k], rounds ((D_i + 1) v_i words), points (v_i),
+ * table_evals (M_i: every pool table fully bound, i.e. its extension at the reversed point), final_evals[k] =
+ * sum_t alpha_t prod_j table_evals[idx(t, j)].  With one term, alpha = 1 and distinct tables these are the product entry's words.
+ * Schedule: per round one small copy, one data pass that loads, binds and stores every pool table of every live instance once and
+ * multiplies out all terms, and one small finish launch; the workspace is 2 M_i ns[i] bytes per live instance.  The caller's
+ * tables are only read.
+ * Every argument is checked for every instance before anything is launched or written; the first failing instance's index goes to
+ * *bad_index (if non-NULL): ZIGZ_ERR_INVALID_ARGUMENT for ctx or an array NULL (fixed_challenges excepted), k > ZIGZ_BATCH_MAX, M_i
+ * or T_i outside 1..8, a term degree outside 1..ZIGZ_PRODUCT_MAX_DEGREE, a pool index >= M_i, a table that is NULL or not 16-byte
+ * aligned, ns[i] > 2^ZIGZ_PRODUCT_MAX_LOG2_N, live instances that together make 2^24 chunks of 8192 elements or more;
+ * ZIGZ_ERR_NO_VARIABLES for ns[i] == 1; ZIGZ_ERR_LENGTH_NOT_POWER_OF_TWO; ZIGZ_ERR_NOT_CANONICAL for a coefficient or a fixed
+ * challenge >= p.  k == 0 returns ZIGZ_OK and touches nothing.  Leaves alone what the product entry leaves alone. */
+#define ZIGZ_SOP_MAX_TABLES 8
+#define ZIGZ_SOP_MAX_TERMS 8
+zigz_status zigz_dev_sumcheck_prove_sop_batch(zigz_ctx *ctx, size_t k, const unsigned *n_tables, const uint32_t *const *d_tables,
+                                              const size_t *ns, const unsigned *n_terms, const unsigned *term_degrees,
+                                              const uint8_t *term_tables, const uint64_t *term_coeffs,
+                                              const uint64_t *fixed_challenges, uint64_t *claimed_sums, uint64_t *rounds,
+                                              uint64_t *points, uint64_t *table_evals, uint64_t *final_evals, size_t *bad_index);
+/* host tables (canonical u64, ZIGZ_ERR_NOT_CANONICAL with the instance's index otherwise), narrowed and uploaded in one copy */
+zigz_status zigz_sumcheck_prove_sop_batch(zigz_ctx *ctx, size_t k, const unsigned *n_tables, const uint64_t *const *tables,
+                                          const size_t *ns, const unsigned *n_terms, const unsigned *term_degrees,
+                                          const uint8_t *term_tables, const uint64_t *term_coeffs, const uint64_t *fixed_challenges,
+                                          uint64_t *claimed_sums, uint64_t *rounds, uint64_t *points, uint64_t *table_evals,
+                                          uint64_t *final_evals, size_t *bad_index);
+
+/* k independent verifications of the proofs zigz_dev_sumcheck_prove_sop_batch writes, as zigz_dev_sumcheck_verify_product_batch
+ * verifies a product proof: the prover's layout, and per POOL ENTRY table_kinds (sum M_i bytes, or NULL: all tables) --
+ * ZIGZ_FACTOR_TABLE, the table at d_tables, or ZIGZ_FACTOR_EQ, eq(tau, .) without the table: its d_tables entry must be NULL and its
+ * tau is the next v_i words of eq_points.  Per proof: the rounds are replayed with D_i + 1 coefficients (a fresh transcript,
+ * claim = claimed_sums[i], reject if g(0) + g(1) != claim, absorb, draw, claim = g(challenge)); every table entry of the pool is
+ * evaluated ONCE at q -- the proof's point as given (flags == 0) or reversed (ZIGZ_SUMCHECK_VERIFY_POINT_REVERSED: where the prover's
+ * evaluations live) -- in the batched eval's launch, one (table, q) pair per pool entry, all proofs together; eq entries on the
+ * host in closed form; the oracle is sum_t alpha_t prod_j oracle[idx(t, j)].  The proof is accepted iff the rounds held, the oracle
+ * equals the last claim and final_evals[i] and, when table_evals != NULL, every entry's oracle equals its table eval.  (A
+ * zero-check's soundness also needs claimed_sums[i] == 0: that comparison is the caller's.)
+ * Outputs: verdicts[k] (may be NULL) 1 accept / 0 reject; *n_rejected; expected_evals[k] (may be NULL) the claim at the failing
+ * round, or the final claim; oracle_evals (sum M_i words, may be NULL) every pool entry's evaluation, written for every proof
+ * including the rejected ones.  A call without a table entry launches nothing.
+ * Statuses are for the shape of the arguments only; everything is checked for every proof before anything is launched or
+ * written, and the first failing proof's index goes to *bad_index (if non-NULL): ZIGZ_ERR_INVALID_ARGUMENT for ctx or n_rejected
+ * NULL, an unknown flag, a NULL input array when k > 0 (table_kinds, eq_points and table_evals excepted), k > ZIGZ_BATCH_MAX, M_i or
+ * T_i outside 1..8, a term degree outside 1..ZIGZ_PRODUCT_MAX_DEGREE, a pool index >= M_i, an unknown kind, an eq entry whose pointer
+ * is not NULL or that has no eq_points, a table entry that is NULL or not 16-byte aligned, ns[i] > 2^32, or table entries that
+ * together make 2^24 chunks of 8192 elements or more; the prover's rules per table (ns[i] == 1 is ZIGZ_ERR_NO_VARIABLES);
+ * ZIGZ_ERR_NOT_CANONICAL for any word of a proof, a coefficient or a tau >= p.  k == 0: ZIGZ_OK, *n_rejected = 0, nothing else
+ * touched. */
+zigz_status zigz_dev_sumcheck_verify_sop_batch(zigz_ctx *ctx, size_t k, const unsigned *n_tables, const uint32_t *const *d_tables,
+                                               const uint8_t *table_kinds, const uint64_t *eq_points, const size_t *ns,
+                                               const unsigned *n_terms, const unsigned *term_degrees, const uint8_t *term_tables,
+                                               const uint64_t *term_coeffs, const uint64_t *claimed_sums, const uint64_t *rounds,
+                                               const uint64_t *points, const uint64_t *table_evals, const uint64_t *final_evals,
+                                               uint32_t flags, uint8_t *verdicts, uint64_t *expected_evals, uint64_t *oracle_evals,
+                                               size_t *n_rejected, size_t *bad_index);
+/* host tables (canonical u64, ZIGZ_ERR_NOT_CANONICAL with the proof's index otherwise), narrowed and uploaded in one copy */
+zigz_status zigz_sumcheck_verify_sop_batch(zigz_ctx *ctx, size_t k, const unsigned *n_tables, const uint64_t *const *tables,
+                                           const uint8_t *table_kinds, const uint64_t *eq_points, const size_t *ns,
+                                           const unsigned *n_terms, const unsigned *term_degrees, const uint8_t *term_tables,
+                                           const uint64_t *term_coeffs, const uint64_t *claimed_sums, const uint64_t *rounds,
+                                           const uint64_t *points, const uint64_t *table_evals, const uint64_t *final_evals,
+                                           uint32_t flags, uint8_t *verdicts, uint64_t *expected_evals, uint64_t *oracle_evals,
+                                           size_t *n_rejected, size_t *bad_index);
+
 /* ---------------------------------------------------------------- host SHA3 sponge / transcript
  * FiatShamirTranscript   src/core/hash.zig:255-324 (sequential by construction: stays on the host) */
 zigz_transcript *zigz_transcript_new(void);

@@ -2,7 +2,7 @@
 // Shared by the translation units behind the C ABI of libzigz_hip.so (include/zigz_hip.h) -- api.cpp (contexts, workspaces,
 // boundary conversion, transcript), api_mle.cpp (MLE ops, the GPU passes of the sumcheck), api_commit.cpp (Merkle trees, commit
 // jobs), api_misc.cpp (Lasso, the measurement hook), api_batch.cpp, api_merkle_batch.cpp, api_merkle_verify.cpp,
-// api_mle_batch.cpp, api_product.cpp (the batched entries): the context, its workspaces, the error macros and the helpers one
+// api_mle_batch.cpp, api_product.cpp, api_sop.cpp (the batched entries): the context, its workspaces, the error macros and the helpers one
 // unit needs from another.  What needs no HIP lives in headers of its own, testable without a GPU: the host side of every
 // sumcheck in sumcheck_host.hpp (field helpers, argument rule, round step, tail rounds, radix schedules), the plans in
 // commit_plan.hpp, open_plan.hpp and verify_plan.hpp.  No CPU fallback for field or hash work on the data path: the only host
@@ -201,6 +201,11 @@ size_t mle_batch_fill(const uint32_t *const *d_tables, const size_t *ns, size_t 
 zigz_status stage_host_tables(zigz_ctx *ctx, const uint64_t *const *tables, const size_t *ns, size_t count,
                               const std::vector<size_t> &at, uint32_t *h, int slot, const size_t *owner,
                               std::vector<const uint32_t *> &d, size_t *bad_index);
+// m (table, point) pairs through the batched eval's launches (api_mle_batch.cpp): the values are at *results once `done` is
+// published; host tables are staged first, a value >= p reported with owner[pair]
+zigz_status mle_eval_pairs_queue(zigz_ctx *ctx, const void *const *tables, bool host_tables, const size_t *ns, size_t m,
+                                 const uint64_t *points, bool reversed, const size_t *owner, const uint64_t **results, DoneFlag *done,
+                                 size_t *bad_index);
 extern std::atomic<int> g_sleep_wait;
 #pragma GCC visibility pop
 

@@ -148,6 +148,32 @@ zigz_status verify_batch(zigz_ctx *ctx, const uint32_t *const *d_tables, const u
     ZIGZ_NOTHROW_END(ctx)
 }
 
+}  // namespace
+
+// m (table, point) pairs of a verifier through the eval's copy and two launches (the product and sum-of-products verifiers: one
+// pair per table oracle of every proof): host tables are narrowed and uploaded first (a value >= p: ZIGZ_ERR_NOT_CANONICAL with
+// owner[pair] in *bad_index).  The m values are at *results once `done` is published.  m == 0 queues nothing.
+zigz_status mle_eval_pairs_queue(zigz_ctx *ctx, const void *const *tables, bool host_tables, const size_t *ns, size_t m,
+                                 const uint64_t *points, bool reversed, const size_t *owner, const uint64_t **results, DoneFlag *done,
+                                 size_t *bad_index) {
+    Layout L;
+    CHK(plan(ns, m, host_tables, L));
+    if (!m) return ZIGZ_OK;
+    uint8_t *pin;
+    CHK(pinned(ctx, L.bytes, &pin));
+    std::vector<const uint32_t *> d;
+    if (host_tables) {
+        CHK(stage_host_tables(ctx, (const uint64_t *const *)tables, ns, m, L.at, (uint32_t *)(pin + L.tab_off), WS_MLEBATCH_IN, owner, d,
+                              bad_index));
+    } else {
+        d.assign((const uint32_t *const *)tables, (const uint32_t *const *)tables + m);
+    }
+    *results = (const uint64_t *)pin;
+    return eval_queue(ctx, L, pin, d.data(), ns, points, reversed, done);
+}
+
+namespace {
+
 // ---- product proofs: the oracles are the proofs' factors, a table (one pair of the eval launch) or eq(tau, .) (host, closed form)
 zigz_status verify_product_batch(zigz_ctx *ctx, const pv::VerifyArgs &a, bool host_tables, uint8_t *verdicts,
                                  uint64_t *expected_evals, uint64_t *oracle_evals, size_t *n_rejected, size_t *bad_index) {
@@ -181,21 +207,10 @@ zigz_status verify_product_batch(zigz_ctx *ctx, const pv::VerifyArgs &a, bool ho
         eoff[i + 1] = eoff[i] + neq * v;
     }
     const size_t m = tabs.size();
-    Layout L;
-    CHK(plan(pair_ns.data(), m, host_tables, L));
     DoneFlag done;
-    uint8_t *pin = nullptr;
-    if (m) {  // (a call without a table factor launches nothing)
-        CHK(pinned(ctx, L.bytes, &pin));
-        std::vector<const uint32_t *> d;
-        if (host_tables) {
-            CHK(stage_host_tables(ctx, (const uint64_t *const *)tabs.data(), pair_ns.data(), m, L.at, (uint32_t *)(pin + L.tab_off),
-                                  WS_MLEBATCH_IN, owner.data(), d, bad_index));
-        } else {
-            d.assign((const uint32_t *const *)tabs.data(), (const uint32_t *const *)tabs.data() + m);
-        }
-        CHK(eval_queue(ctx, L, pin, d.data(), pair_ns.data(), pair_points.data(), reversed, &done));
-    }
+    const uint64_t *pairs = nullptr;
+    CHK(mle_eval_pairs_queue(ctx, tabs.data(), host_tables, pair_ns.data(), m, pair_points.data(), reversed, owner.data(), &pairs, &done,
+                             bad_index));
     // the k replays and the eq factors, underneath the evaluation
     std::vector<sv::Replay> rep(k);
     std::vector<uint64_t> ev(foff[k], 0);
@@ -210,7 +225,6 @@ zigz_status verify_product_batch(zigz_ctx *ctx, const pv::VerifyArgs &a, bool ho
             }
     });
     if (m) CHK(wait_published(ctx, done));
-    const uint64_t *pairs = (const uint64_t *)pin;
     size_t rejected = 0;
     for (size_t i = 0; i < k; i++) {
         for (size_t f = foff[i]; f < foff[i + 1]; f++)

@@ -611,4 +611,45 @@ void launch_product_finish(const ProductTab *d_tabs, unsigned nt, const unsigned
 // one workgroup per instance: its d tables (m <= 1024 values each) into pinned memory as u32, table j at tail_off + j m
 void launch_product_tails(const ProductTab *d_tabs, unsigned nt, uint32_t *h_dst, hipStream_t s, DoneFlag done);
 
+// ---- batched sum-of-products sumcheck (sumcheck_sop.hip): sum_x sum_t alpha_t prod_j pool[idx(t, j)](x) for k
+// independent instances, a pool of up to SOP_MAX_TABLES tables and up to SOP_MAX_TERMS terms of degree 1..3 each.  The product
+// prover's layout and schedule (a workgroup owns one chunk of PRODUCT_CHUNK elements of one instance's current tables); every
+// pool table is loaded, bound and stored ONCE per round however many terms name it.  sop_host.hpp holds the host side.
+constexpr unsigned SOP_MAX_TABLES = 8;  // ZIGZ_SOP_MAX_TABLES
+constexpr unsigned SOP_MAX_TERMS = 8;   // ZIGZ_SOP_MAX_TERMS
+// sums per workgroup / result words per instance: the coefficient sums of the terms of degree 1 (2 words), 2 (3) and 3 (4), apart,
+// because a sum of degree-d terms carries R^-d (sumcheck_product.hip); class d starts at word SOP_CLASS_AT[d - 1]
+constexpr unsigned SOP_SUMS = 2 + 3 + 4;
+constexpr unsigned SOP_CLASS_AT[PRODUCT_MAX_DEGREE] = {0, 2, 5};
+struct SopTerm {
+    uint32_t w;       // degree | idx_0 << 8 | idx_1 << 16 | idx_2 << 24 (pool indices of the term's factors)
+    uint32_t coef_m;  // alpha_t, Montgomery form
+};
+inline uint32_t sop_term_word(unsigned degree, const uint8_t *idx) {
+    uint32_t w = degree;
+    for (unsigned j = 0; j < degree; j++) w |= (uint32_t)idx[j] << (8 + 8 * j);
+    return w;
+}
+struct SopTab {  // one instance in one pass; its workgroups are [first_wg, first_wg of instance j + 1)
+    const uint32_t *in[SOP_MAX_TABLES];  // the pool tables the pass reads: m packed canonical values each, 16-byte aligned
+    uint32_t *out[SOP_MAX_TABLES];       // bind pass: the bound tables (m / 2 values); out[j] == in[j] binds in place
+    SopTerm term[SOP_MAX_TERMS];
+    uint64_t m;                          // current length, a power of two (> 1024 in the sums and bind passes)
+    uint64_t tail_off;                   // tails pass: first word of the instance's tables in the published u32 array
+    uint32_t n_tables, n_terms;
+    uint32_t n_d1, n_d2;                 // term[] is sorted by degree: n_d1 linear terms, then n_d2 quadratic ones, then the cubic ones
+    uint32_t r_m;                        // bind pass: the challenge the tables are bound with, Montgomery form
+    uint32_t first_wg;
+    uint32_t slot;                       // the instance's SOP_SUMS result words start at out + SOP_SUMS * slot
+    uint32_t pad_;
+};
+// round 0: part[SOP_SUMS wg + c] = the workgroup's exact sum of class-coefficient c over its index pairs (i, i + m / 2)
+void launch_sop_sums(const SopTab *d_tabs, unsigned nt, unsigned nwg, unsigned long long *d_part, hipStream_t s);
+// a later round: binds every pool table with r_m and sums the class coefficients of the BOUND tables' pairs (q, q + m/4)
+void launch_sop_bind(const SopTab *d_tabs, unsigned nt, unsigned nwg, unsigned long long *d_part, hipStream_t s);
+// one workgroup per instance: its workgroups' partials added, reduced mod p once, into out[SOP_SUMS slot + c] (pinned host memory)
+void launch_sop_finish(const SopTab *d_tabs, unsigned nt, const unsigned long long *d_part, uint64_t *out, hipStream_t s, DoneFlag done);
+// one workgroup per instance: its pool tables (m <= 1024 values each) into pinned memory as u32, table j at tail_off + j m
+void launch_sop_tails(const SopTab *d_tabs, unsigned nt, uint32_t *h_dst, hipStream_t s, DoneFlag done);
+
 }  // namespace zk

@@ -36,8 +36,7 @@
 // nothing has to be zeroed between rounds or calls.
 #include "kernels.hpp"
 
-#include "field.hpp"
-#include "tree_dev.hpp"
+#include "product_dev.hpp"  // PdAcc, pd_add, pd_terms, pd_bind4 (with field.hpp, tree_dev.hpp)
 
 namespace zk {
 
@@ -51,44 +50,6 @@ static_assert(TPB == 256, "four wave sums per workgroup and coefficient");
 static_assert(2 + (PRODUCT_MAX_LOG2_N - 1) + 31 < 64, "a coefficient's exact u64 sum: 3 * 2^29 * 2^31 < 2^64");
 // a lane's deferred sums: at most 2 products per pair and coefficient, 4 pairs per vector -> lo < 2^5 2^32, hi < 2^5 2^31
 static_assert(PD_SUM_ITERS * 4 * 2 <= 32 && PD_BIND_ITERS * 4 * 2 <= 32, "hi + monty_reduce(lo) < 2^37 < p 2^32");
-
-template <int D>
-struct PdAcc {
-    unsigned long long lo[D + 1], hi[D + 1];
-};
-
-__device__ __forceinline__ void pd_add(unsigned long long &lo, unsigned long long &hi, uint32_t x, uint32_t y) {
-    const unsigned long long pr = (unsigned long long)x * y;
-    lo += (uint32_t)pr;
-    hi += pr >> 32;
-}
-
-// the terms of one index pair: a[j] = f_j at the low index, b[j] at the high one, canonical
-template <int D>
-__device__ __forceinline__ void pd_terms(const uint32_t (&a)[D], const uint32_t (&b)[D], PdAcc<D> &s) {
-    uint32_t e[D];
-#pragma unroll
-    for (int j = 0; j < D; j++) e[j] = sub_mod(b[j], a[j]);
-    if constexpr (D == 1) {
-        s.lo[0] += a[0];
-        s.lo[1] += e[0];
-    } else if constexpr (D == 2) {
-        pd_add(s.lo[0], s.hi[0], a[0], a[1]);
-        pd_add(s.lo[1], s.hi[1], a[0], e[1]);
-        pd_add(s.lo[1], s.hi[1], e[0], a[1]);
-        pd_add(s.lo[2], s.hi[2], e[0], e[1]);
-    } else {
-        const uint32_t p = mont_mul(a[0], a[1]), q = mont_mul(e[0], e[1]);
-        // a0 e1 + e0 a1 < 2 p^2 < p 2^32
-        const uint32_t x = monty_reduce((unsigned long long)a[0] * e[1] + (unsigned long long)e[0] * a[1]);
-        pd_add(s.lo[0], s.hi[0], p, a[2]);
-        pd_add(s.lo[1], s.hi[1], p, e[2]);
-        pd_add(s.lo[1], s.hi[1], x, a[2]);
-        pd_add(s.lo[2], s.hi[2], x, e[2]);
-        pd_add(s.lo[2], s.hi[2], q, a[2]);
-        pd_add(s.lo[3], s.hi[3], q, e[2]);
-    }
-}
 
 template <int D>
 __device__ __forceinline__ void pd_terms4(const uint4 (&a)[D], const uint4 (&b)[D], PdAcc<D> &s) {
@@ -105,10 +66,6 @@ __device__ __forceinline__ void pd_terms4(const uint4 (&a)[D], const uint4 (&b)[
 #pragma unroll
     for (int j = 0; j < D; j++) { x[j] = a[j].w; y[j] = b[j].w; }
     pd_terms<D>(x, y, s);
-}
-
-__device__ __forceinline__ uint4 pd_bind4(const uint4 &a, const uint4 &b, uint32_t r_m) {
-    return make_uint4(bind1(a.x, b.x, r_m), bind1(a.y, b.y, r_m), bind1(a.z, b.z, r_m), bind1(a.w, b.w, r_m));
 }
 
 // the lane's sums -> canonical values, added over the workgroup, one store per coefficient at part[PRODUCT_SUMS wg + c]

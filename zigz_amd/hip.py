@@ -582,6 +582,113 @@ class Context:
         return self._verify_product_batch(lib.zigz_dev_sumcheck_verify_product_batch, ptrs, [len(inst) for inst in d_instances], kinds,
                                           taus, ns, proofs, flags, check_factor_evals)
 
+    # ---- batched sum-of-products sumcheck: a pool of tables and terms alpha * prod pool[idx] per instance
+    @staticmethod
+    def _sop_terms(all_terms):
+        """the flat term arrays of the entries: (n_terms, term_degrees, term_tables, term_coeffs) and the ctypes views that own them"""
+        k = len(all_terms)
+        nt = (C.c_uint * max(k, 1))(*[len(terms) for terms in all_terms])
+        flat = [(int(alpha), [int(x) for x in idx]) for terms in all_terms for alpha, idx in terms]
+        dg = (C.c_uint * max(len(flat), 1))(*[len(idx) for _, idx in flat])
+        ix = np.array([x for _, idx in flat for x in idx] + [0], dtype=np.uint8)
+        co, cop = _u64(np.array([alpha for alpha, _ in flat] + [0], dtype=np.uint64))
+        return nt, dg, (ix, ix.ctypes.data_as(u8p)), (co, cop)
+
+    @staticmethod
+    def _sop_degrees(all_terms):
+        return [max([len(idx) for _, idx in terms] + [0]) for terms in all_terms]
+
+    def _sop_batch(self, fn, ptrs, pool_sizes, all_terms, ns, challenges):
+        k = len(ns)
+        nvs = [max(int(n).bit_length() - 1, 0) for n in ns]
+        degrees = self._sop_degrees(all_terms)
+        nm = (C.c_uint * max(k, 1))(*[int(m) for m in pool_sizes])
+        nsa = (C.c_size_t * max(k, 1))(*[int(n) for n in ns])
+        nt, dg, (ix, ixp), (co, cop) = self._sop_terms(all_terms)
+        cs, csp = _out_u64(k)
+        r, rp = _out_u64(sum((d + 1) * v for d, v in zip(degrees, nvs)))
+        pt, ptp = _out_u64(sum(nvs))
+        tv, tvp = _out_u64(sum(pool_sizes))
+        fe, fep = _out_u64(k)
+        cp = None
+        if challenges is not None:
+            c, cp = self._cat_u64(challenges)
+        bad = C.c_size_t(0)
+        self.check_batch(fn(self.h, k, nm, ptrs, nsa, nt, dg, ixp, cop, cp, csp, rp, ptp, tvp, fep, C.byref(bad)), bad)
+        out, ro, vo, mo = [], 0, 0, 0
+        for i, (d, v, m) in enumerate(zip(degrees, nvs, pool_sizes)):
+            out.append((int(cs[i]), r[ro: ro + (d + 1) * v].copy(), pt[vo: vo + v].copy(), tv[mo: mo + m].copy(), int(fe[i])))
+            ro, vo, mo = ro + (d + 1) * v, vo + v, mo + m
+        return out
+
+    def sumcheck_prove_sop_batch(self, instances, challenges=None):
+        """zigz_sumcheck_prove_sop_batch: instances[i] = (tables, terms) -- a pool of 1..8 equally long tables and 1..8 terms
+        (alpha, (idx, ...)), each a coefficient times the product of 1..3 pool tables named by index; the instance proves
+        sum_x sum_t alpha_t prod_j tables[idx_j](x).  challenges[i] (optional) fixes instance i's challenges.  Returns per
+        instance (claimed_sum, rounds [(D + 1) words per round, D the largest term degree], point, table_evals [one per pool
+        table], final_eval)."""
+        arrs = [_u64(t) for tables, _ in instances for t in tables]
+        ptrs = (u64p * max(len(arrs), 1))(*[p for _, p in arrs])
+        return self._sop_batch(lib.zigz_sumcheck_prove_sop_batch, ptrs, [len(tables) for tables, _ in instances],
+                               [terms for _, terms in instances], [len(tables[0]) if len(tables) else 0 for tables, _ in instances],
+                               challenges)
+
+    def dev_sumcheck_prove_sop_batch(self, d_instances, ns, challenges=None):
+        """zigz_dev_sumcheck_prove_sop_batch: d_instances[i] = (device tables, terms), the tables packed u32 canonical, 16-byte
+        aligned, ns[i] values each; read only."""
+        flat = [int(d) for tables, _ in d_instances for d in tables]
+        ptrs = (vp * max(len(flat), 1))(*flat)
+        return self._sop_batch(lib.zigz_dev_sumcheck_prove_sop_batch, ptrs, [len(tables) for tables, _ in d_instances],
+                               [terms for _, terms in d_instances], ns, challenges)
+
+    def _verify_sop_batch(self, fn, ptrs, pool_sizes, kinds, taus, all_terms, ns, proofs, flags, check_table_evals):
+        k = len(ns)
+        nm = (C.c_uint * max(k, 1))(*[int(m) for m in pool_sizes])
+        nsa = (C.c_size_t * max(k, 1))(*[int(n) for n in ns])
+        nt, dg, (ix, ixp), (co, cop) = self._sop_terms(all_terms)
+        kn = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint8).reshape(-1) for x in kinds] + [np.zeros(1, np.uint8)]))
+        tp = None
+        if taus is not None:
+            tq, tp = self._cat_u64(taus)
+        cs, csp = self._cat_u64([[int(p[0]) for p in proofs]])
+        r, rp = self._cat_u64([p[1] for p in proofs])
+        q, qp = self._cat_u64([p[2] for p in proofs])
+        tv, tvp = self._cat_u64([p[3] for p in proofs])
+        fe, fep = self._cat_u64([[int(p[4]) for p in proofs]])
+        verd, vdp = _out_u8(k)
+        exp, ep = _out_u64(k)
+        orc, op = _out_u64(sum(pool_sizes))
+        rej, bad = C.c_size_t(0), C.c_size_t(0)
+        self.check_batch(fn(self.h, k, nm, ptrs, kn.ctypes.data_as(u8p), tp, nsa, nt, dg, ixp, cop, csp, rp, qp,
+                            tvp if check_table_evals else None, fep, int(flags), vdp, ep, op, C.byref(rej), C.byref(bad)), bad)
+        oracle, o = [], 0
+        for m in pool_sizes:
+            oracle.append([int(x) for x in orc[o: o + m]])
+            o += m
+        return verd[:k].copy(), [int(x) for x in exp[:k]], oracle, rej.value
+
+    def sumcheck_verify_sop_batch(self, instances, proofs, flags=0, taus=None, check_table_evals=True):
+        """zigz_sumcheck_verify_sop_batch: proofs[i] = (claimed_sum, rounds, point, table_evals, final_eval) as
+        sumcheck_prove_sop_batch returns it, instances[i] = (pool, terms) with a pool entry a table, or None for eq(tau, .), whose
+        tau is the next entry of `taus`.  flags as sumcheck_verify_batch's.  Returns (verdicts np.uint8, expected_evals,
+        oracle_evals [one per pool entry and proof], n_rejected)."""
+        arrs = [(None, None) if t is None else _u64(t) for tables, _ in instances for t in tables]
+        ptrs = (u64p * max(len(arrs), 1))(*[p for _, p in arrs])
+        kinds = [[1 if t is None else 0 for t in tables] for tables, _ in instances]
+        ns = [1 << len(p[2]) if all(t is None for t in tables) else len(next(t for t in tables if t is not None))
+              for (tables, _), p in zip(instances, proofs)]
+        return self._verify_sop_batch(lib.zigz_sumcheck_verify_sop_batch, ptrs, [len(tables) for tables, _ in instances], kinds, taus,
+                                      [terms for _, terms in instances], ns, proofs, flags, check_table_evals)
+
+    def dev_sumcheck_verify_sop_batch(self, d_instances, ns, proofs, flags=0, taus=None, check_table_evals=True):
+        """zigz_dev_sumcheck_verify_sop_batch: d_instances[i] = (pool, terms), the pool's entries device addresses (packed u32
+        canonical, 16-byte aligned, ns[i] values) or None for eq(tau, .)."""
+        flat = [d for tables, _ in d_instances for d in tables]
+        ptrs = (vp * max(len(flat), 1))(*[None if d is None else int(d) for d in flat])
+        kinds = [[1 if d is None else 0 for d in tables] for tables, _ in d_instances]
+        return self._verify_sop_batch(lib.zigz_dev_sumcheck_verify_sop_batch, ptrs, [len(tables) for tables, _ in d_instances], kinds,
+                                      taus, [terms for _, terms in d_instances], ns, proofs, flags, check_table_evals)
+
     def _merkle_batch_out(self, rc, bad, k, roots, heights, handle, ns, keep):
         self.check_batch(rc, bad)
         res = [(roots[32 * i: 32 * (i + 1)].tobytes(), int(heights[i])) for i in range(k)]
