@@ -776,6 +776,75 @@ zigz_status zigz_sumcheck_verify_sop_batch(zigz_ctx *ctx, size_t k, const unsign
                                            uint32_t flags, uint8_t *verdicts, uint64_t *expected_evals, uint64_t *oracle_evals,
                                            size_t *n_rejected, size_t *bad_index);
 
+/* k independent ZERO-CHECK sumchecks with the eq factor in closed form: instance i proves
+ *   S_i = sum_{x in {0,1}^v_i} eq(tau_i, x) C_i(x),   C_i(x) = sum_{t < T_i} alpha_t prod_{j < d_t} pool[idx(t, j)](x),
+ * over zigz_dev_sumcheck_prove_sop_batch's pool of M_i tables (1..8, NONE of them eq) and T_i terms (1..8) of degree d_t in
+ * 1..ZIGZ_PRODUCT_MAX_DEGREE, with the same layout, index and coefficient rules.  tau_i is the next v_i canonical words of eq_points,
+ * tau[0] going with the LSB of x as in zigz_dev_eq_table_batch.  No eq table is built, bound or stored: round r binds index bit
+ * v - 1 - r (the MSB-first bind), so the weight factors as s_r(X) = P_r ((1 - tau_j) + (2 tau_j - 1) X) t_r(X) with j = v - 1 - r,
+ * P_r the product of eq(tau_{v-1-r'}, challenge_r') over the rounds so far, and t_r the round polynomial of C weighted pair by pair
+ * with the eq table of the PREFIX tau_0..tau_{v-r-2}, which the passes form from two small tables.  The proof is word for word the
+ * one the sop entry writes with the materialised eq table appended to the pool and named by every term -- but C may have degree 3:
+ * a round has D_i + 2 coefficients c_0..c_{D+1}, D_i = max_t d_t, at most ZIGZ_ZEROCHECK_MAX_DEGREE + 1.  A fresh transcript per
+ * instance absorbs all D_i + 2 coefficients in order and then draws; fixed_challenges != NULL as there.
+ * Outputs: claimed_sums[k], rounds ((D_i + 2) v_i words), points (v_i), table_evals (M_i: every pool table fully bound, i.e. at
+ * the reversed point), eq_evals[k] = eq(tau_i, .) at the reversed point, final_evals[k] = eq_evals[i] * sum_t alpha_t prod_j
+ * table_evals[idx(t, j)].  Schedule and limits are the sop entry's (instances longer than 1024 on the device, one small copy, one
+ * data pass and one finish launch per round, the tails on the host after one hand-off; the weights travel with the first copy);
+ * the workspace is 2 M_i ns[i] bytes per live instance.  The caller's tables are only read.
+ * Every argument is checked for every instance before anything is launched or written, with the sop entry's statuses in its order
+ * (eq_points and eq_evals must not be NULL); then, per instance, ZIGZ_ERR_NOT_CANONICAL for a tau word >= p.  k == 0 returns
+ * ZIGZ_OK and touches nothing. */
+#define ZIGZ_ZEROCHECK_MAX_DEGREE 4
+zigz_status zigz_dev_sumcheck_prove_zerocheck_batch(zigz_ctx *ctx, size_t k, const unsigned *n_tables, const uint32_t *const *d_tables,
+                                                    const size_t *ns, const unsigned *n_terms, const unsigned *term_degrees,
+                                                    const uint8_t *term_tables, const uint64_t *term_coeffs, const uint64_t *eq_points,
+                                                    const uint64_t *fixed_challenges, uint64_t *claimed_sums, uint64_t *rounds,
+                                                    uint64_t *points, uint64_t *table_evals, uint64_t *eq_evals, uint64_t *final_evals,
+                                                    size_t *bad_index);
+/* host tables (canonical u64, ZIGZ_ERR_NOT_CANONICAL with the instance's index otherwise), narrowed and uploaded in one copy */
+zigz_status zigz_sumcheck_prove_zerocheck_batch(zigz_ctx *ctx, size_t k, const unsigned *n_tables, const uint64_t *const *tables,
+                                                const size_t *ns, const unsigned *n_terms, const unsigned *term_degrees,
+                                                const uint8_t *term_tables, const uint64_t *term_coeffs, const uint64_t *eq_points,
+                                                const uint64_t *fixed_challenges, uint64_t *claimed_sums, uint64_t *rounds,
+                                                uint64_t *points, uint64_t *table_evals, uint64_t *eq_evals, uint64_t *final_evals,
+                                                size_t *bad_index);
+
+/* k independent verifications of the proofs zigz_dev_sumcheck_prove_zerocheck_batch writes, as zigz_dev_sumcheck_verify_sop_batch
+ * verifies a sop proof: the prover's layout and eq_points.  Per proof: the rounds are replayed with D_i + 2 coefficients (a fresh
+ * transcript, claim = claimed_sums[i], reject if g(0) + g(1) != claim, absorb, draw, claim = g(challenge)); every pool table is
+ * evaluated ONCE at q -- the proof's point as given (flags == 0) or reversed (ZIGZ_SUMCHECK_VERIFY_POINT_REVERSED: where the
+ * prover's evaluations live) -- in the batched eval's launch; eq(tau_i, q) on the host in closed form; the oracle is eq(tau_i, q) *
+ * sum_t alpha_t prod_j oracle[idx(t, j)].  The proof is accepted iff the rounds held, the oracle equals the last claim and
+ * final_evals[i], and every given eval (table_evals, eq_evals: each may be NULL) equals its oracle.  (A zero-check's soundness also
+ * needs claimed_sums[i] == 0: that comparison is the caller's.)
+ * Outputs: verdicts[k] (may be NULL); *n_rejected; expected_evals[k] (may be NULL) the claim at the failing round, or the final
+ * claim; oracle_evals (sum M_i words, may be NULL) every pool table's evaluation, written for every proof.  A call with no
+ * instances launches nothing.
+ * Statuses are for the shape of the arguments only, checked for every proof before anything is launched or written; the first
+ * failing proof's index goes to *bad_index (if non-NULL): ZIGZ_ERR_INVALID_ARGUMENT for ctx or n_rejected NULL, an unknown flag, a
+ * NULL input array when k > 0 (table_evals and eq_evals excepted), k > ZIGZ_BATCH_MAX, M_i or T_i outside 1..8, a term degree
+ * outside 1..ZIGZ_PRODUCT_MAX_DEGREE, a pool index >= M_i, a table that is NULL or not 16-byte aligned, ns[i] > 2^32, or tables that
+ * together make 2^24 chunks of 8192 elements or more; the prover's rules per table (ns[i] == 1 is ZIGZ_ERR_NO_VARIABLES);
+ * ZIGZ_ERR_NOT_CANONICAL for any word of a proof, a coefficient or a tau >= p.  k == 0: ZIGZ_OK, *n_rejected = 0, nothing else
+ * touched. */
+zigz_status zigz_dev_sumcheck_verify_zerocheck_batch(zigz_ctx *ctx, size_t k, const unsigned *n_tables, const uint32_t *const *d_tables,
+                                                     const uint64_t *eq_points, const size_t *ns, const unsigned *n_terms,
+                                                     const unsigned *term_degrees, const uint8_t *term_tables,
+                                                     const uint64_t *term_coeffs, const uint64_t *claimed_sums, const uint64_t *rounds,
+                                                     const uint64_t *points, const uint64_t *table_evals, const uint64_t *eq_evals,
+                                                     const uint64_t *final_evals, uint32_t flags, uint8_t *verdicts,
+                                                     uint64_t *expected_evals, uint64_t *oracle_evals, size_t *n_rejected,
+                                                     size_t *bad_index);
+/* host tables (canonical u64, ZIGZ_ERR_NOT_CANONICAL with the proof's index otherwise), narrowed and uploaded in one copy */
+zigz_status zigz_sumcheck_verify_zerocheck_batch(zigz_ctx *ctx, size_t k, const unsigned *n_tables, const uint64_t *const *tables,
+                                                 const uint64_t *eq_points, const size_t *ns, const unsigned *n_terms,
+                                                 const unsigned *term_degrees, const uint8_t *term_tables, const uint64_t *term_coeffs,
+                                                 const uint64_t *claimed_sums, const uint64_t *rounds, const uint64_t *points,
+                                                 const uint64_t *table_evals, const uint64_t *eq_evals, const uint64_t *final_evals,
+                                                 uint32_t flags, uint8_t *verdicts, uint64_t *expected_evals, uint64_t *oracle_evals,
+                                                 size_t *n_rejected, size_t *bad_index);
+
 /* ---------------------------------------------------------------- host SHA3 sponge / transcript
  * FiatShamirTranscript   src/core/hash.zig:255-324 (sequential by construction: stays on the host) */
 zigz_transcript *zigz_transcript_new(void);

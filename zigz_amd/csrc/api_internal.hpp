@@ -2,7 +2,7 @@
 // Shared by the translation units behind the C ABI of libzigz_hip.so (include/zigz_hip.h) -- api.cpp (contexts, workspaces,
 // boundary conversion, transcript), api_mle.cpp (MLE ops, the GPU passes of the sumcheck), api_commit.cpp (Merkle trees, commit
 // jobs), api_misc.cpp (Lasso, the measurement hook), api_batch.cpp, api_merkle_batch.cpp, api_merkle_verify.cpp,
-// api_mle_batch.cpp, api_product.cpp, api_sop.cpp (the batched entries): the context, its workspaces, the error macros and the helpers one
+// api_mle_batch.cpp, api_product.cpp, api_sop.cpp, api_zerocheck.cpp (the batched entries): the context, its workspaces, the error macros and the helpers one
 // unit needs from another.  What needs no HIP lives in headers of its own, testable without a GPU: the host side of every
 // sumcheck in sumcheck_host.hpp (field helpers, argument rule, round step, tail rounds, radix schedules), the plans in
 // commit_plan.hpp, open_plan.hpp and verify_plan.hpp.  No CPU fallback for field or hash work on the data path: the only host

@@ -652,4 +652,16 @@ void launch_sop_finish(const SopTab *d_tabs, unsigned nt, const unsigned long lo
 // one workgroup per instance: its pool tables (m <= 1024 values each) into pinned memory as u32, table j at tail_off + j m
 void launch_sop_tails(const SopTab *d_tabs, unsigned nt, uint32_t *h_dst, hipStream_t s, DoneFlag done);
 
+// ---- zero-check with the eq factor in closed form (sumcheck_zerocheck.hip): the sop passes with every index
+// pair x of the round weighted by W[x] = lo[x & 1023] * hi[x >> 10], the eq table of a prefix of tau that is never materialised.
+// An instance's descriptor is a SopTab (pool without eq; the finish and tails launches are the sop ones) plus its weights:
+constexpr unsigned ZC_LOG2_LO = 10;  // zc::LOG2_LO: a lane's 16-byte vectors of one trip cover 1024 consecutive pairs
+struct ZcWeights {
+    const uint32_t *lo;  // eq(tau_0 .. tau_9, .): 1024 words, Montgomery form, 16-byte aligned; the same in every round
+    const uint32_t *hi;  // the stage of the round the pass sums for: (pairs of that round) / 1024 words, Montgomery form
+};
+// round 0 and a later round, as launch_sop_sums / launch_sop_bind; d_w[j] goes with d_tabs[j]
+void launch_zc_sums(const SopTab *d_tabs, const ZcWeights *d_w, unsigned nt, unsigned nwg, unsigned long long *d_part, hipStream_t s);
+void launch_zc_bind(const SopTab *d_tabs, const ZcWeights *d_w, unsigned nt, unsigned nwg, unsigned long long *d_part, hipStream_t s);
+
 }  // namespace zk

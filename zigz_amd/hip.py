@@ -689,6 +689,96 @@ class Context:
         return self._verify_sop_batch(lib.zigz_dev_sumcheck_verify_sop_batch, ptrs, [len(tables) for tables, _ in d_instances], kinds,
                                       taus, [terms for _, terms in d_instances], ns, proofs, flags, check_table_evals)
 
+    # ---- zero-check with the eq factor in closed form: a pool WITHOUT eq, terms of degree 1..3 and tau per instance
+    def _zerocheck_batch(self, fn, ptrs, pool_sizes, all_terms, taus, ns, challenges):
+        k = len(ns)
+        nvs = [max(int(n).bit_length() - 1, 0) for n in ns]
+        degrees = self._sop_degrees(all_terms)
+        nm = (C.c_uint * max(k, 1))(*[int(m) for m in pool_sizes])
+        nsa = (C.c_size_t * max(k, 1))(*[int(n) for n in ns])
+        nt, dg, (ix, ixp), (co, cop) = self._sop_terms(all_terms)
+        tq, tp = self._cat_u64(taus)
+        cs, csp = _out_u64(k)
+        r, rp = _out_u64(sum((d + 2) * v for d, v in zip(degrees, nvs)))
+        pt, ptp = _out_u64(sum(nvs))
+        tv, tvp = _out_u64(sum(pool_sizes))
+        ee, eep = _out_u64(k)
+        fe, fep = _out_u64(k)
+        cp = None
+        if challenges is not None:
+            c, cp = self._cat_u64(challenges)
+        bad = C.c_size_t(0)
+        self.check_batch(fn(self.h, k, nm, ptrs, nsa, nt, dg, ixp, cop, tp, cp, csp, rp, ptp, tvp, eep, fep, C.byref(bad)), bad)
+        out, ro, vo, mo = [], 0, 0, 0
+        for i, (d, v, m) in enumerate(zip(degrees, nvs, pool_sizes)):
+            out.append((int(cs[i]), r[ro: ro + (d + 2) * v].copy(), pt[vo: vo + v].copy(), tv[mo: mo + m].copy(), int(ee[i]), int(fe[i])))
+            ro, vo, mo = ro + (d + 2) * v, vo + v, mo + m
+        return out
+
+    def sumcheck_prove_zerocheck_batch(self, instances, challenges=None):
+        """zigz_sumcheck_prove_zerocheck_batch: instances[i] = (tables, terms, tau) -- a pool of 1..8 equally long tables (none of
+        them eq), 1..8 terms (alpha, (idx, ...)) of degree 1..3 as sumcheck_prove_sop_batch takes them, and tau (log2 n canonical
+        words, tau[0] with the LSB); the instance proves sum_x eq(tau, x) sum_t alpha_t prod_j tables[idx_j](x) without an eq
+        table.  Returns per instance (claimed_sum, rounds [(D + 2) words per round, D the largest term degree], point,
+        table_evals [one per pool table], eq_eval, final_eval)."""
+        arrs = [_u64(t) for tables, _, _ in instances for t in tables]
+        ptrs = (u64p * max(len(arrs), 1))(*[p for _, p in arrs])
+        return self._zerocheck_batch(lib.zigz_sumcheck_prove_zerocheck_batch, ptrs, [len(tables) for tables, _, _ in instances],
+                                     [terms for _, terms, _ in instances], [tau for _, _, tau in instances],
+                                     [len(tables[0]) if len(tables) else 0 for tables, _, _ in instances], challenges)
+
+    def dev_sumcheck_prove_zerocheck_batch(self, d_instances, ns, challenges=None):
+        """zigz_dev_sumcheck_prove_zerocheck_batch: d_instances[i] = (device tables, terms, tau), the tables packed u32 canonical,
+        16-byte aligned, ns[i] values each; read only."""
+        flat = [int(d) for tables, _, _ in d_instances for d in tables]
+        ptrs = (vp * max(len(flat), 1))(*flat)
+        return self._zerocheck_batch(lib.zigz_dev_sumcheck_prove_zerocheck_batch, ptrs, [len(tables) for tables, _, _ in d_instances],
+                                     [terms for _, terms, _ in d_instances], [tau for _, _, tau in d_instances], ns, challenges)
+
+    def _verify_zerocheck_batch(self, fn, ptrs, pool_sizes, all_terms, taus, ns, proofs, flags, check_table_evals, check_eq_evals):
+        k = len(ns)
+        nm = (C.c_uint * max(k, 1))(*[int(m) for m in pool_sizes])
+        nsa = (C.c_size_t * max(k, 1))(*[int(n) for n in ns])
+        nt, dg, (ix, ixp), (co, cop) = self._sop_terms(all_terms)
+        tq, tp = self._cat_u64(taus)
+        cs, csp = self._cat_u64([[int(p[0]) for p in proofs]])
+        r, rp = self._cat_u64([p[1] for p in proofs])
+        q, qp = self._cat_u64([p[2] for p in proofs])
+        tv, tvp = self._cat_u64([p[3] for p in proofs])
+        ee, eep = self._cat_u64([[int(p[4]) for p in proofs]])
+        fe, fep = self._cat_u64([[int(p[5]) for p in proofs]])
+        verd, vdp = _out_u8(k)
+        exp, ep = _out_u64(k)
+        orc, op = _out_u64(sum(pool_sizes))
+        rej, bad = C.c_size_t(0), C.c_size_t(0)
+        self.check_batch(fn(self.h, k, nm, ptrs, tp, nsa, nt, dg, ixp, cop, csp, rp, qp, tvp if check_table_evals else None,
+                            eep if check_eq_evals else None, fep, int(flags), vdp, ep, op, C.byref(rej), C.byref(bad)), bad)
+        oracle, o = [], 0
+        for m in pool_sizes:
+            oracle.append([int(x) for x in orc[o: o + m]])
+            o += m
+        return verd[:k].copy(), [int(x) for x in exp[:k]], oracle, rej.value
+
+    def sumcheck_verify_zerocheck_batch(self, instances, proofs, flags=0, check_table_evals=True, check_eq_evals=True):
+        """zigz_sumcheck_verify_zerocheck_batch: proofs[i] = (claimed_sum, rounds, point, table_evals, eq_eval, final_eval) as
+        sumcheck_prove_zerocheck_batch returns it, instances[i] = (tables, terms, tau).  flags as sumcheck_verify_batch's.
+        Returns (verdicts np.uint8, expected_evals, oracle_evals [one per pool table and proof], n_rejected)."""
+        arrs = [_u64(t) for tables, _, _ in instances for t in tables]
+        ptrs = (u64p * max(len(arrs), 1))(*[p for _, p in arrs])
+        return self._verify_zerocheck_batch(lib.zigz_sumcheck_verify_zerocheck_batch, ptrs, [len(tables) for tables, _, _ in instances],
+                                            [terms for _, terms, _ in instances], [tau for _, _, tau in instances],
+                                            [len(tables[0]) if len(tables) else 0 for tables, _, _ in instances], proofs, flags,
+                                            check_table_evals, check_eq_evals)
+
+    def dev_sumcheck_verify_zerocheck_batch(self, d_instances, ns, proofs, flags=0, check_table_evals=True, check_eq_evals=True):
+        """zigz_dev_sumcheck_verify_zerocheck_batch: d_instances[i] = (device tables, terms, tau), the tables packed u32 canonical,
+        16-byte aligned, ns[i] values each."""
+        flat = [d for tables, _, _ in d_instances for d in tables]
+        ptrs = (vp * max(len(flat), 1))(*[None if d is None else int(d) for d in flat])
+        return self._verify_zerocheck_batch(lib.zigz_dev_sumcheck_verify_zerocheck_batch, ptrs,
+                                            [len(tables) for tables, _, _ in d_instances], [terms for _, terms, _ in d_instances],
+                                            [tau for _, _, tau in d_instances], ns, proofs, flags, check_table_evals, check_eq_evals)
+
     def _merkle_batch_out(self, rc, bad, k, roots, heights, handle, ns, keep):
         self.check_batch(rc, bad)
         res = [(roots[32 * i: 32 * (i + 1)].tobytes(), int(heights[i])) for i in range(k)]
