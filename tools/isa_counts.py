@@ -111,7 +111,7 @@ def keccak_per_hash(counts):
 
 def main():
     counts = count(assembly())
-    sel = {k: v for k, v in counts.items() if "keccak" in k or "bind" in k or "sums" in k or "radix" in k or "witness" in k
+    sel = {k: v for k, v in counts.items() if "keccak" in k or "bind" in k or "sums" in k or "radix" in k or "k_eval_" in k or "witness" in k
            or "lasso" in k or "k_level_hash" in k or "k_merkle_top" in k or "k_runs_" in k or "k_cons_" in k}
     doc = {"source": "zigz_amd/csrc/kernels.hip + merkle_levels.hip, hipcc --offload-arch=gfx950 -O3 (tools/isa_counts.py)",
            "kernels": sel}

@@ -835,12 +835,13 @@ extern "C" zigz_status zigz_commit_open_all(zigz_commit_job *job, const uint64_t
         const size_t n_const = use ? job->const_cols : 0;
         if (arena || use) ctx->stats.eval_constant_columns = n_const;
         CHK(timed_begin(ctx, 4));
-        if (arena) CHK(dev_eval_radix(ctx, job->d_cols, job->col_stride, ncols, nv, points, z_val, &skip, n_const));
-        else CHK(dev_eval_folds(ctx, job->d_cols, job->col_stride, ncols, nv, points, z_val, use ? &skip : nullptr, n_const));
+        EvalFinish fin;  // (the radix form leaves the values to the paths launch: one evaluation launch instead of four)
+        if (arena) CHK(dev_eval_radix(ctx, job->d_cols, job->col_stride, ncols, nv, points, z_val, &skip, n_const, &fin));
+        else CHK(dev_eval_folds(ctx, job->d_cols, job->col_stride, ncols, nv, points, z_val, use ? &skip : nullptr, n_const, &fin));
         CHK(timed_end(ctx, 4, &ctx->stats.eval_us));
         const DoneFlag done = done_flag(ctx, 1);
         launch_paths(job->tree, job->tree.npad, (unsigned)nv, job->d_cols, job->col_stride, h_idx, z_sib, z_dirs, z_leaf,
-                     job->zstride ? job->ncols1 : ncols, ctx->stream, done);
+                     job->zstride ? job->ncols1 : ncols, ctx->stream, done, &fin);
         HIPCHK(ctx, hipGetLastError());
         if (!(g_sleep_wait.load() && !ctx->timing && sleep_wait(done.flag, done.seq)))
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));

@@ -170,10 +170,13 @@ zigz_status bind_launch(zigz_ctx *ctx, const uint32_t *d_in, size_t in_stride, u
 void bind_pool_reset(zigz_ctx *ctx);
 zigz_status bind_pool_collect(zigz_ctx *ctx);
 zigz_status dev_eval_radix(zigz_ctx *ctx, const uint32_t *d_cols, size_t col_stride, size_t ncols, size_t nv,
-                                  const uint64_t *points, uint32_t *d_vals, const EvalSkip *skip = nullptr, size_t n_const = 0);
-// skip, n_const: the columns the eval may leave out and how many of them there are (sizes the launch)
+                                  const uint64_t *points, uint32_t *d_vals, const EvalSkip *skip = nullptr, size_t n_const = 0,
+                                  EvalFinish *fin = nullptr);
+// fin: the caller's next launch on the stream is launch_paths with *fin -- the radix form may then be ONE launch that leaves the
+// values to it (fin->part != nullptr afterwards); skip, n_const: the columns the eval may leave out and how many of them there are (sizes the launch)
 zigz_status dev_eval_folds(zigz_ctx *ctx, const uint32_t *d_cols, size_t col_stride, size_t ncols, size_t nv,
-                                  const uint64_t *points /*host, ncols*nv*/, uint32_t *d_vals, const EvalSkip *skip = nullptr, size_t n_const = 0);
+                                  const uint64_t *points /*host, ncols*nv*/, uint32_t *d_vals, const EvalSkip *skip = nullptr, size_t n_const = 0,
+                                  EvalFinish *fin = nullptr);
 zigz_status sumcheck_core(zigz_ctx *ctx, const uint32_t *d_in, size_t n, uint32_t *d_scratch,
                                  const uint64_t *fixed, uint64_t *rounds, uint64_t *point, uint64_t *final_eval);
 zigz_status stage_in(zigz_ctx *ctx, const uint64_t *in, size_t n, uint32_t **d_out);

@@ -149,7 +149,7 @@ extern "C" zigz_status zigz_dev_mle_bind_sums(zigz_ctx *ctx, const uint32_t *d_i
 // leaving 1024 elements per column that a weighted dot product with the eq weights of point[9..0] finishes.
 // HBM traffic 4*N B per column instead of 12*N for v successive binds.  Exact arithmetic => same value.
 zigz_status dev_eval_radix(zigz_ctx *ctx, const uint32_t *d_cols, size_t col_stride, size_t ncols, size_t nv,
-                                  const uint64_t *points, uint32_t *d_vals, const EvalSkip *skip, size_t n_const) {
+                                  const uint64_t *points, uint32_t *d_vals, const EvalSkip *skip, size_t n_const, EvalFinish *fin) {
     const size_t N = (size_t)1 << nv;
     const unsigned k2 = 10, k1 = (unsigned)nv - k2;
     const size_t m = (size_t)1 << k2, nb = (size_t)1 << k1;
@@ -169,6 +169,34 @@ zigz_status dev_eval_radix(zigz_ctx *ctx, const uint32_t *d_cols, size_t col_str
     // zero-copy: k_eq_weights reads the few KB of points from the pinned buffer (both callers wait for the stream before they
     // return, so the buffer is not rewritten under it)
     const uint32_t *d_rt = rt;
+    // A commit job's openings (fin): ONE launch, finished by the paths launch that follows.  Taken for every shape the radix form
+    // serves -- its grid is k_radix_fold's, (row group, column), so no shape fills the chip better with the four launches below,
+    // and with few workgroups the three launches saved are all the more of the time (reasoned, not measured at the smallest
+    // shapes: nv = 14 with one active column is a single workgroup either way); only a build with -DZK_EVAL_FOUR_LAUNCHES
+    // (A/B) keeps them.  Every other caller (one table, the batched entries) has no launch behind it that could finish.
+    const int ro = fin ? eval_onepass_rloops(nb, rloops) : 0;
+    if (ro) {
+        const size_t g1 = nb / ((size_t)16 * ro);
+        void *wp;
+        CHK(ws_get(ctx, WS_FOLD, ncols * g1 * 8 + 256, &wp));
+        bind_pool_reset(ctx);
+        const bool rec1 = ctx->timing;
+        launch_eval_onepass(d_cols, col_stride, (unsigned)nv, d_rt, (unsigned long long *)wp, (unsigned)g1, ncols, ctx->stream,
+                            rec1 ? ctx->pool[0] : nullptr, rec1 ? ctx->pool[1] : nullptr, skip, ro);
+        if (rec1) {
+            ctx->pool_used = 1;
+            ctx->pool_is_fold = ctx->active_job != nullptr;
+            ctx->pool_bytes = (uint64_t)(ncols - (skip ? n_const : 0)) * (N * 4 + g1 * 8);  // one read of the tables + the partials
+        }
+        HIPCHK(ctx, hipGetLastError());
+        fin->part = (const unsigned long long *)wp;
+        fin->groups = (unsigned)g1;
+        fin->skip = skip ? *skip : EvalSkip();
+        fin->out = d_vals;
+        fin->cols = skip ? d_cols : nullptr;
+        fin->col_stride = col_stride;
+        return ZIGZ_OK;
+    }
     // workspace: part[ncols][groups][m] u64 | W1[ncols][nb] u32 | W2[ncols][m] u32 | T1[ncols][m] u32
     void *ws;
     CHK(ws_get(ctx, WS_FOLD, ncols * (groups * m * 8 + nb * 4 + m * 4 + m * 4) + 256, &ws));
@@ -198,7 +226,8 @@ zigz_status dev_eval_radix(zigz_ctx *ctx, const uint32_t *d_cols, size_t col_str
 // point reversed (exact arithmetic => the same canonical value as the reference's O(v*2^v) loop).
 // Batched over `ncols` columns, column c using point row c.  Result words land in d_vals[ncols].
 zigz_status dev_eval_folds(zigz_ctx *ctx, const uint32_t *d_cols, size_t col_stride, size_t ncols, size_t nv,
-                                  const uint64_t *points /*host, ncols*nv*/, uint32_t *d_vals, const EvalSkip *skip, size_t n_const) {
+                                  const uint64_t *points /*host, ncols*nv*/, uint32_t *d_vals, const EvalSkip *skip, size_t n_const,
+                                  EvalFinish *fin) {
     const size_t N = (size_t)1 << nv;
     if (nv == 0) {
         launch_gather_first(d_cols, col_stride, d_vals, ncols, ctx->stream);
@@ -206,7 +235,7 @@ zigz_status dev_eval_folds(zigz_ctx *ctx, const uint32_t *d_cols, size_t col_str
         return ZIGZ_OK;
     }
     if (nv >= 14 && nv <= 24 && col_stride % 4 == 0 && aligned16(d_cols) && !ctx->fold_eval)
-        return dev_eval_radix(ctx, d_cols, col_stride, ncols, nv, points, d_vals, skip, n_const);
+        return dev_eval_radix(ctx, d_cols, col_stride, ncols, nv, points, d_vals, skip, n_const, fin);
     // r table in Montgomery form, [round][col], staged in the upper half of the pinned buffer so the
     // asynchronous H2D copy never reads freed host memory
     if (nv * ncols * 4 > PIN_WORDS * 8 / 2) return ZIGZ_ERR_INVALID_ARGUMENT;

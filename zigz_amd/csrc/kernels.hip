@@ -5,7 +5,8 @@
 //  K2/K3  k_block_sums / k_half_sums_small  round-polynomial half sums, block sums   HBM-bound, 4 B/element
 //  K5     k_keccak_leaves             SHA3-256 leaf hashes                      int-VALU bound
 //  K6     k_keccak_level / _top       SHA3-256 level merges                     int-VALU bound
-//  K7     k_paths                     authentication-path gather               latency
+//  K4     k_eval_onepass              a commit job's opening evaluation, one launch   HBM-bound, 4 B/element
+//  K7     k_paths                     authentication-path gather (+ K4's last sum)   latency
 //  K9     k_lasso_fingerprints        XXH3-64 row fingerprints                  int-VALU bound
 #include "kernels.hpp"
 #include <hip/hip_ext.h>
@@ -337,6 +338,98 @@ __global__ __launch_bounds__(TPB) void k_radix_fold(const uint32_t *__restrict__
     ulonglong2 *o = reinterpret_cast<ulonglong2 *>(part + col * part_col_stride + (size_t)blockIdx.y * m + q * 4);
     o[0] = make_ulonglong2(s[0], s[1]);
     o[1] = make_ulonglong2(s[2], s[3]);
+}
+
+// The opening evaluation of a commit job (kernels.hpp: EvalFinish): k_radix_fold<true>'s pass over the data with the weights
+// built by the workgroup itself and the low ten variables folded in before anything is written -- no weight tables and no
+// 1024-vector of partial sums in HBM, and the launches around the pass (k_eq_weights2, k_radix_finalize, k_weighted_dot) gone.
+// With m = 1024 a workgroup holds the whole 1024-vector of its rows, four entries per thread.  W1[b] = prod_j (bit k1-1-j of b
+// ? r_j : 1 - r_j) over the k1 = nv - 10 high variables, one row per thread of the first wave; W2[i] = A[i >> 5] B[i & 31], two
+// 32-entry tables of five variables each, built by the second wave.  The first chunk's loads are in flight under all of that.
+__global__ __launch_bounds__(TPB) void k_eval_onepass(const uint32_t *__restrict__ in, size_t in_stride, unsigned nv,
+                                                      const uint32_t *__restrict__ r_m, unsigned long long *__restrict__ part,
+                                                      unsigned groups, EvalSkip skip, int rloops) {
+    ZK_PRIO_SMALL();
+    __shared__ uint32_t s_r[32], s_w1[RB * RLOOPS], s_a[32], s_b[32];
+    __shared__ unsigned long long s_red[TPB / 64];
+    const size_t col = blockIdx.z;
+    if (eval_skips(skip, col)) return;  // (workgroup-uniform) a constant column: k_paths stores its first element
+    const unsigned t = threadIdx.x, k1 = nv - 10, rows = (unsigned)RB * (unsigned)rloops;
+    const size_t mq = 1024 / 4, row0 = (size_t)blockIdx.y * rows;
+    const uint4 *p = reinterpret_cast<const uint4 *>(in + eval_col_off(skip, col, in_stride)) + t;
+    uint4 v[RB];
+#pragma unroll
+    for (int j = 0; j < RB; j++) v[j] = ZK_STREAM_LOAD(p + (row0 + j) * mq);
+    if (t < nv) s_r[t] = r_m[col * nv + t];
+    __syncthreads();
+    if (t < rows) {
+        const size_t b = row0 + t;
+        uint32_t w = R_MOD_P;
+        for (unsigned j = 0; j < k1; j++) w = mont_mul(w, ((b >> (k1 - 1 - j)) & 1) ? s_r[j] : sub_mod(R_MOD_P, s_r[j]));
+        s_w1[t] = w;
+    } else if (t >= 64 && t < 128) {
+        const unsigned x = t & 31, j0 = k1 + (t >= 96 ? 5 : 0);
+        uint32_t w = R_MOD_P;
+        for (unsigned j = 0; j < 5; j++) w = mont_mul(w, ((x >> (4 - j)) & 1) ? s_r[j0 + j] : sub_mod(R_MOD_P, s_r[j0 + j]));
+        (t >= 96 ? s_b : s_a)[x] = w;
+    }
+    __syncthreads();
+    unsigned long long lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};  // (the deferred reduction of k_radix_fold: <= 64 terms)
+#pragma unroll 1
+    for (int l = 0; l < rloops; l++) {
+        if (l) {
+#pragma unroll
+            for (int j = 0; j < RB; j++) v[j] = ZK_STREAM_LOAD(p + (row0 + (size_t)l * RB + j) * mq);
+        }
+#pragma unroll
+        for (int j = 0; j < RB; j++) {
+            const uint32_t wj = s_w1[l * RB + j];
+            const uint32_t e[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                const unsigned long long pr = (unsigned long long)wj * e[c];
+                lo[c] += (uint32_t)pr;
+                hi[c] += pr >> 32;
+            }
+        }
+    }
+    unsigned long long acc = 0;  // < 4 p
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const uint32_t sum = (uint32_t)((hi[c] + monty_reduce(lo[c])) % (unsigned long long)P);
+        const unsigned i = 4 * t + c;
+        acc += mont_mul(mont_mul(s_a[i >> 5], s_b[i & 31]), sum);
+    }
+    acc = wave_sum(acc);
+    if ((t & 63) == 0) s_red[t >> 6] = acc;
+    __syncthreads();
+    if (t == 0) {
+        unsigned long long tot = 0;
+        for (int w = 0; w < TPB / 64; w++) tot += s_red[w];
+        part[col * groups + blockIdx.y] = tot;  // < 1024 p: a column's <= 1024 partials add up below 2^64
+    }
+}
+int eval_onepass_rloops(size_t nb, int rloops) {
+#ifdef ZK_EVAL_FOUR_LAUNCHES
+    (void)nb;
+    (void)rloops;
+    return 0;
+#else
+    if (rloops <= 0 || rloops > RLOOPS) rloops = RLOOPS;
+    int r = 1;
+    while (r * 2 <= rloops && nb % ((size_t)RB * r * 2) == 0) r *= 2;
+    return nb % ((size_t)RB * r) == 0 ? r : 0;
+#endif
+}
+void launch_eval_onepass(const uint32_t *d_in, size_t in_stride, unsigned nv, const uint32_t *d_r_m, unsigned long long *d_part,
+                         unsigned groups, size_t ncols, hipStream_t s, hipEvent_t t_start, hipEvent_t t_stop, const EvalSkip *skip,
+                         int rloops) {
+    const dim3 grid(1, groups, (unsigned)ncols);
+    const EvalSkip sk = skip ? *skip : EvalSkip();
+    if (t_start && t_stop)
+        hipExtLaunchKernelGGL(k_eval_onepass, grid, dim3(TPB), 0, s, t_start, t_stop, 0, d_in, in_stride, nv, d_r_m, d_part, groups, sk, rloops);
+    else
+        hipLaunchKernelGGL(k_eval_onepass, grid, dim3(TPB), 0, s, d_in, in_stride, nv, d_r_m, d_part, groups, sk, rloops);
 }
 
 size_t radix_fold_groups(size_t nb, int rloops) {
@@ -1035,7 +1128,7 @@ void launch_keccak_small_l01(const uint32_t *d_vals, size_t val_stride, size_t n
 // (completion flags of launches that publish into pinned host memory: signal_done / signal_done_block, tree_dev.hpp)
 __global__ __launch_bounds__(64) void k_paths(TreeRef t, size_t n_values, unsigned height, const uint32_t *__restrict__ vals,
                                               size_t val_stride, const uint64_t *__restrict__ idx, uint8_t *__restrict__ sib,
-                                              uint8_t *__restrict__ dirs, uint32_t *__restrict__ leaf, DoneFlag done) {
+                                              uint8_t *__restrict__ dirs, uint32_t *__restrict__ leaf, DoneFlag done, EvalFinish fin) {
     ZK_PRIO_SMALL();
     const size_t col = blockIdx.x;
     const size_t fc = (size_t)blockIdx.z * gridDim.x + col;  // a batched job: proof blockIdx.z; results are numbered proof by proof
@@ -1057,14 +1150,24 @@ __global__ __launch_bounds__(64) void k_paths(TreeRef t, size_t n_values, unsign
         q[1] = make_ulonglong2(d.w[2], d.w[3]);
         dirs[fc * height + l] = (uint8_t)(ci & 1);  // directions[l] = is_right
     }
+    if (fin.part) {  // the column's opened value: the partials of k_eval_onepass, or the first element of a constant column
+        if (fin.cols && eval_skips(fin.skip, fc)) {
+            if (l == 0) fin.out[fc] = fin.cols[eval_col_off(fin.skip, fc, fin.col_stride)];
+        } else {
+            unsigned long long a = 0;
+            for (unsigned g = l; g < fin.groups; g += 64) a += fin.part[fc * fin.groups + g];
+            a = wave_sum(a);
+            if (l == 0) fin.out[fc] = (uint32_t)(a % (unsigned long long)P);
+        }
+    }
     signal_done(done, gridDim.x * gridDim.z);
 }
 
 void launch_paths(const TreeRef &t, size_t n_values, unsigned height, const uint32_t *d_vals, size_t val_stride,
                   const uint64_t *d_idx, uint8_t *d_sib, uint8_t *d_dirs, uint32_t *d_leaf, size_t ncols, hipStream_t s,
-                  DoneFlag done) {
+                  DoneFlag done, const EvalFinish *fin) {
     hipLaunchKernelGGL(k_paths, dim3((unsigned)ncols, 1, t.nz ? t.nz : 1), dim3(64), 0, s, t, n_values, height, d_vals, val_stride, d_idx,
-                       d_sib, d_dirs, d_leaf, done);
+                       d_sib, d_dirs, d_leaf, done, fin ? *fin : EvalFinish());
 }
 // Many openings of a job's trees (zigz_commit_open_many).  The work item is 16 bytes of one sibling digest, numbered along the
 // proof's descriptors: item = (descriptor e, level l, half); all paths have nv levels, so consecutive lanes store consecutive

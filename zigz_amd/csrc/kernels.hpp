@@ -125,6 +125,26 @@ struct EvalSkip {
     unsigned ncols1 = 0;
     size_t z_in = 0, z_changed = 0;
 };
+// The opening evaluation of a commit job in ONE pass and ONE launch (k_eval_onepass; m = 1024, 14 <= nv <= 24): workgroup
+// (g, c) builds the eq weights of its rows and of the low ten variables itself, folds its rows of column c and writes one exact
+// u64 partial, part[c * groups + g] = sum_i W2[i] * ((sum_{b in g} W1[b] in[c][b * 1024 + i]) mod p); the paths launch that
+// follows on the stream adds a column's partials, reduces mod p and stores the value (EvalFinish) before it signals completion.
+// r_m: [column][nv] coordinates in Montgomery form, variable j = point[nv - 1 - j] (may be pinned host memory: read once per
+// workgroup).  rloops: 16-row chunks per workgroup, nb % (16 rloops) == 0 (eval_onepass_rloops).
+struct EvalFinish {
+    const unsigned long long *part = nullptr;  // nullptr: the values were stored by the evaluation's own launches
+    unsigned groups = 0;
+    EvalSkip skip;                  // a skipped column's value is its first element
+    uint32_t *out = nullptr;        // [column]
+    const uint32_t *cols = nullptr; // the committed table (proof 0's in a batched job), for the skipped columns
+    size_t col_stride = 0;
+};
+// 16-row chunks per workgroup of the one-pass evaluation of nb rows when the four-launch route would take `rloops` (the
+// largest power of two <= rloops that divides nb / 16); 0: the build keeps the four launches (-DZK_EVAL_FOUR_LAUNCHES, A/B)
+int eval_onepass_rloops(size_t nb, int rloops);
+void launch_eval_onepass(const uint32_t *d_in, size_t in_stride, unsigned nv, const uint32_t *d_r_m, unsigned long long *d_part,
+                         unsigned groups, size_t ncols, hipStream_t s, hipEvent_t t_start, hipEvent_t t_stop, const EvalSkip *skip,
+                         int rloops);
 void launch_radix_fold(const uint32_t *d_in, size_t in_stride, size_t m, size_t nb, const uint32_t *d_w_m,
                        size_t w_stride, unsigned long long *d_part, size_t part_col_stride, size_t ncols, hipStream_t s,
                        hipEvent_t t_start = nullptr, hipEvent_t t_stop = nullptr, const EvalSkip *skip = nullptr, int rloops = 0);
@@ -385,7 +405,7 @@ void launch_publish_u64(unsigned long long *d_src, size_t n, unsigned long long 
 void launch_publish_u32(const uint32_t *d_src, size_t n, uint32_t *h_dst, hipStream_t s, DoneFlag done);
 void launch_paths(const TreeRef &t, size_t n_values, unsigned height, const uint32_t *d_vals, size_t val_stride,
                   const uint64_t *d_idx, uint8_t *d_sib, uint8_t *d_dirs, uint32_t *d_leaf, size_t ncols, hipStream_t s,
-                  DoneFlag done = DoneFlag());
+                  DoneFlag done = DoneFlag(), const EvalFinish *fin = nullptr);  // fin: also finishes a one-pass evaluation
 // Many openings of a commit job's trees (zigz_commit_open_many): descriptor e of proof z (descriptors zf.first[z] ..
 // zf.first[z + 1], grid z = proof) opens column `tree` of that proof at `index`; its nv siblings go to slot off * nv of d_sib /
 // d_dirs, its leaf value to d_leaf[off].  Digests are found through node_ptr like K7's; same output-major lanes as above.
