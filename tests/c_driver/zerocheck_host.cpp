@@ -12,7 +12,9 @@
 //                    and the shorter rounds by zc::tail_rounds, as the library hands over.
 //                  A third line holds zc::verdict over the first proof with its own evaluations as oracles: as is, with final_eval + 1,
 //                  with eq_eval + 1.
-//   check          runs the argument checkers on bad shapes and prints "case status bad_index" per case (bad_index -1: untouched).
+//   check          checks the stage every pass of a live instance reads (zc::stage, zc::weight_words) against the stages there are, at
+//                  every v from 11 to ZIGZ_PRODUCT_MAX_LOG2_N (exit status 6); then runs the argument checkers on bad shapes and
+//                  prints "case status bad_index" per case (bad_index -1: untouched).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -334,7 +336,32 @@ void run_verify_case(const char *name, Batch &b, uint32_t flags, bool no_rejecte
     }
 }
 
+// The stage a pass reads, at every live length of an instance of 2^v values (round 0 at 2^v, then one bind pass per length down
+// to 2048): the stage's first word and the pairs / 1024 words (at least one) the pass reads from it lie inside the hi stages
+// build_weights wrote and inside the instance's share of the weights region, whose size keeps the next instance's lo 16-byte aligned
+bool stages_in_bounds() {
+    const size_t lo = (size_t)1 << zc::LOG2_LO;
+    for (unsigned v = zc::LOG2_LO + 1; v <= ZIGZ_PRODUCT_MAX_LOG2_N; v++) {
+        const size_t n = (size_t)1 << v, words = zc::weight_words(n), hi = zc::hi_words(v, zc::LOG2_LO);
+        if (words % 4 || lo + hi > words) {
+            fprintf(stderr, "weight_words(2^%u) = %zu: not a multiple of 4 words, or short of lo + %zu\n", v, words, hi);
+            return false;
+        }
+        for (int bind = 0; bind < 2; bind++)
+            for (size_t m = n; m > HOST_TAIL_MAX; m = bind ? m / 2 : HOST_TAIL_MAX) {
+                const size_t reads = std::max(zc::pairs(m, bind) / lo, (size_t)1), end = zc::stage_at(zc::stage(m, bind)) + reads;
+                if (end > hi || lo + end > words) {
+                    fprintf(stderr, "v %u, %s pass at m = %zu: stage %u, words [%zu, %zu) of %zu hi words\n", v, bind ? "bind" : "sums", m,
+                            zc::stage(m, bind), zc::stage_at(zc::stage(m, bind)), end, hi);
+                    return false;
+                }
+            }
+    }
+    return true;
+}
+
 int check() {
+    if (!stages_in_bounds()) return 6;
     const uint64_t p = ZIGZ_BABYBEAR_P;
     for (int dev = 0; dev < 2; dev++) {
         { Batch b; run_case("ok", b, dev); }

@@ -2,8 +2,9 @@
 // Shared by the translation units behind the C ABI of libzigz_hip.so (include/zigz_hip.h) -- api.cpp (contexts, workspaces,
 // boundary conversion, transcript), api_mle.cpp (MLE ops, the GPU passes of the sumcheck), api_commit.cpp (Merkle trees, commit
 // jobs), api_misc.cpp (Lasso, the measurement hook), api_batch.cpp, api_merkle_batch.cpp, api_merkle_verify.cpp,
-// api_mle_batch.cpp, api_product.cpp, api_sop.cpp, api_zerocheck.cpp (the batched entries): the context, its workspaces, the error macros and the helpers one
-// unit needs from another.  What needs no HIP lives in headers of its own, testable without a GPU: the host side of every
+// api_mle_batch.cpp, api_product.cpp, api_sop.cpp, api_zerocheck.cpp (the batched entries; the last three share the round schedule
+// and the pool verifier of product_schedule.hpp): the context, its workspaces, the error macros and the helpers one unit needs
+// from another.  What needs no HIP lives in headers of its own, testable without a GPU: the host side of every
 // sumcheck in sumcheck_host.hpp (field helpers, argument rule, round step, tail rounds, radix schedules), the plans in
 // commit_plan.hpp, open_plan.hpp and verify_plan.hpp.  No CPU fallback for field or hash work on the data path: the only host
 // arithmetic is the sequential SHA3 Fiat-Shamir sponge (K11) and O(v) scalar bookkeeping.
@@ -220,6 +221,15 @@ template <class Check>
 zigz_status host_checks(zigz_ctx *ctx, const uint64_t *const *tables, const size_t *ns, size_t k, size_t *bad_index, Check check) {
     bool value;
     const zigz_status st = checks_in_call_order(tables, ns, k, bad_index, check, &value);
+    if (value) set_err(ctx, "%s", NOT_CANONICAL_TEXT);
+    return st;
+}
+// ... and the host form of a family whose checker walks its own layout: check(&value) returns the status and says whether it is
+// a table's value >= p
+template <class Check>
+zigz_status host_value_checks(zigz_ctx *ctx, Check check) {
+    bool value = false;
+    const zigz_status st = check(&value);
     if (value) set_err(ctx, "%s", NOT_CANONICAL_TEXT);
     return st;
 }

@@ -1,18 +1,9 @@
-// C ABI of libzigz_hip.so, part 10: the batched sum-of-products sumcheck prover and its verifier.
-//
-// The prover's schedule is api_product.cpp's, over pools instead of factor lists.  Instances longer than 1024 are LIVE.  Round 0:
-// one copy of the live instances' descriptors, one launch that sums every live instance's class coefficients over the caller's
-// tables and one small launch that reduces them into pinned memory and stores the completion word; the host turns the class sums
-// into c_0..c_D (sop_host.hpp: coefficients) and steps every live transcript on its threads.  Every later round is the same copy
-// and two launches with the fused bind pass in place of the sums: every POOL table is loaded, bound and stored once, whatever
-// number of terms names it (the first bound round writes each table's bound copy, n/2 words, into the workspace -- 2 M n bytes
-// per instance --, the later ones run in place there).  One launch then hands the current tables of ALL instances to the host,
-// which finishes their rounds (sop_host.hpp: tail_rounds).  The workspaces are the product prover's: calls on a context are serial.
-//
-// The verifier replays the rounds on the host's threads while the batched eval's launch (api_mle_batch.cpp) evaluates every table
-// entry of every pool once; eq entries are closed forms on the host; sop_host.hpp's verdict combines them through the terms.
-#include "api_internal.hpp"
-#include "sop_host.hpp"
+// C ABI of libzigz_hip.so, part 10: the batched sum-of-products sumcheck prover and its verifier.  The schedule
+// and the verifier are product_schedule.hpp's; here: what the sop family hands them -- pools instead of factor lists (every POOL
+// table is loaded, bound and stored once per round, whatever number of terms names it: 2 M n bytes of bound copies per instance),
+// class sums to c_0..c_D (sop_host.hpp: coefficients), sop_host.hpp's tail rounds and verdict, eq entries as closed forms -- and
+// the four entries.
+#include "product_schedule.hpp"
 
 using namespace zk;
 
@@ -23,263 +14,76 @@ static_assert(sop::MAX_DEGREE == PRODUCT_MAX_DEGREE && pd::R1 == R_MOD_P, "the h
 
 namespace {
 
-struct Inst {
-    size_t len = 0, tail_off = 0;
-    const uint32_t *cur[SOP_MAX_TABLES] = {};
-    uint32_t *work[SOP_MAX_TABLES] = {};
-    SopTerm term[SOP_MAX_TERMS] = {};  // sorted by degree, as the kernels walk them
-    unsigned n_deg[PRODUCT_MAX_DEGREE] = {};
-    uint64_t ch = 0;  // the challenge of the instance's last round
-    SumcheckRounds pr;
-};
+struct Sop : sched::PoolTerms {
+    static constexpr size_t BEHIND = 0;
+    uint64_t *table_evals, *final_evals;
 
-// one call's pinned region: sums (SOP_SUMS u64 per instance) | tails (u32) | round descriptors | tail descriptors | the narrowed
-// tables of the host form
-struct Layout {
-    size_t tail_off = 0, tail_words = 0, desc_off = 0, tdesc_off = 0, tab_off = 0, tab_words = 0, bytes = 0;
-    size_t nwg = 0, work_words = 0;  // workgroups of round 0; words of all bound copies
-    std::vector<size_t> fns, owner;  // every pool table's length and instance
-    std::vector<size_t> at;          // host form: table f's first word among the narrowed tables (each 16-byte aligned)
+    Sop(const sop::Args &a, uint64_t *table_evals, uint64_t *final_evals)
+        : PoolTerms(a), table_evals(table_evals), final_evals(final_evals) {}
+    unsigned ncoef(size_t i) const { return sh[i].D + 1; }
+    size_t payload_words(size_t) const { return 0; }
+    void payload(size_t, uint32_t *) const {}
+    void behind(size_t, void *, const uint32_t *, size_t, bool) const {}
+    void sums(const SopTab *d, unsigned n, unsigned wg, unsigned long long *part, hipStream_t s) const { launch_sop_sums(d, n, wg, part, s); }
+    void bind(const SopTab *d, unsigned n, unsigned wg, unsigned long long *part, hipStream_t s) const { launch_sop_bind(d, n, wg, part, s); }
+    uint64_t step(size_t i, SumcheckRounds &pr, const uint64_t *sums) const {
+        uint64_t c[SOP_SUMS];
+        sop::coefficients(sh[i].D, sums, c);
+        return pr.step(c);
+    }
+    void finish_tail(size_t i, SumcheckRounds &pr, std::vector<uint64_t> *f) const {
+        final_evals[i] = sop::tail_rounds(pr, f, sh[i].M, sh[i].terms, sh[i].T, table_evals + sh[i].moff);
+    }
 };
-
-zigz_status plan(size_t k, const unsigned *n_tables, const size_t *ns, bool host_tables, Layout &L) {
-    for (size_t i = 0; i < k; i++) {
-        L.tail_words += n_tables[i] * (ns[i] < HOST_TAIL_MAX ? ns[i] : HOST_TAIL_MAX);
-        if (ns[i] > HOST_TAIL_MAX) {
-            L.nwg += product_wgs(ns[i]);
-            L.work_words += n_tables[i] * (ns[i] / 2);
-        }
-        L.fns.insert(L.fns.end(), n_tables[i], ns[i]);
-        L.owner.insert(L.owner.end(), n_tables[i], i);
-    }
-    if (L.nwg > MLE_BATCH_MAX_WGS) return ZIGZ_ERR_INVALID_ARGUMENT;  // one launch: fewer than 2^32 threads in its grid
-    const size_t desc = align256(k * sizeof(SopTab));
-    L.tail_off = align256(k * SOP_SUMS * 8);
-    L.desc_off = L.tail_off + align256(L.tail_words * 4);
-    L.tdesc_off = L.desc_off + desc;
-    L.tab_off = L.tdesc_off + desc;
-    if (host_tables) {
-        L.at = packed_offsets(L.fns.data(), L.fns.size());
-        L.tab_words = L.at[L.fns.size()];
-    }
-    L.bytes = L.tab_off + L.tab_words * 4;
-    return ZIGZ_OK;
-}
 
 zigz_status run(zigz_ctx *ctx, const sop::Args &a, const uint32_t *const *d_tables, const uint64_t *const *h_tables,
                 uint64_t *claimed_sums, uint64_t *rounds, uint64_t *points, uint64_t *table_evals, uint64_t *final_evals,
                 size_t *bad_index) {
     ZIGZ_NOTHROW_BEGIN
-    const size_t k = a.k;
-    Layout L;
-    CHK(plan(k, a.n_tables, a.ns, h_tables != nullptr, L));
-    uint8_t *pin;
-    CHK(pinned(ctx, L.bytes, &pin));
-    std::vector<const uint32_t *> up;
-    if (h_tables) {
-        CHK(stage_host_tables(ctx, h_tables, L.fns.data(), L.fns.size(), L.at, (uint32_t *)(pin + L.tab_off), WS_PRODUCT_IN,
-                              L.owner.data(), up, bad_index));
-        d_tables = up.data();
-    }
-    const size_t desc = L.tdesc_off - L.desc_off;
-    void *d_stage, *d_work;
-    CHK(ws_get(ctx, WS_PRODUCT, 2 * desc + L.nwg * SOP_SUMS * 8, &d_stage));
-    CHK(ws_get(ctx, WS_PRODUCT_WORK, L.work_words * 4, &d_work));
-    const SopTab *d_desc = (const SopTab *)d_stage, *d_tdesc = (const SopTab *)((uint8_t *)d_stage + desc);
-    unsigned long long *d_part = (unsigned long long *)((uint8_t *)d_stage + 2 * desc);
-    SopTab *h_desc = (SopTab *)(pin + L.desc_off), *h_tdesc = (SopTab *)(pin + L.tdesc_off);
-    const uint64_t *h_sums = (const uint64_t *)pin;
-
-    const std::vector<sop::Shape> sh = sop::shapes(k, a.n_tables, a.ns, a.n_terms, a.term_degrees, a.term_tables, a.term_coeffs);
-    std::vector<Inst> t(k);
-    std::vector<size_t> live, next;
-    {
-        size_t woff = 0, toff = 0;
-        for (size_t i = 0; i < k; i++) {
-            Inst &s = t[i];
-            const sop::Shape &h = sh[i];
-            s.len = a.ns[i];
-            s.tail_off = toff;
-            toff += h.M * (a.ns[i] < HOST_TAIL_MAX ? a.ns[i] : HOST_TAIL_MAX);
-            for (unsigned j = 0; j < h.M; j++) {
-                s.cur[j] = d_tables[h.moff + j];
-                if (a.ns[i] > HOST_TAIL_MAX) {  // every table's bound copy is 16-byte aligned: n / 2 >= 1024 words
-                    s.work[j] = (uint32_t *)d_work + woff;
-                    woff += a.ns[i] / 2;
-                }
-            }
-            unsigned nt = 0;
-            for (unsigned d = 1; d <= PRODUCT_MAX_DEGREE; d++)
-                for (unsigned x = 0; x < h.T; x++)
-                    if (h.terms[x].d == d) {
-                        s.term[nt++] = SopTerm{sop_term_word(d, h.terms[x].idx), host_to_mont(h.terms[x].alpha)};
-                        s.n_deg[d - 1]++;
-                    }
-            s.pr.ncoef = h.D + 1;
-            s.pr.nv = h.nv;
-            s.pr.claimed_sum = claimed_sums + i;
-            s.pr.rounds = rounds + h.roff;
-            s.pr.point = points + h.voff;
-            s.pr.fixed = a.fixed ? a.fixed + h.voff : nullptr;
-            if (a.ns[i] > HOST_TAIL_MAX) live.push_back(i);
-        }
-    }
-    // instance i's descriptor with its current tables
-    auto describe = [&](size_t i) {
-        const Inst &s = t[i];
-        SopTab p{};
-        for (unsigned j = 0; j < sh[i].M; j++) p.in[j] = s.cur[j];
-        for (unsigned x = 0; x < sh[i].T; x++) p.term[x] = s.term[x];
-        p.m = s.len;
-        p.n_tables = sh[i].M;
-        p.n_terms = sh[i].T;
-        p.n_d1 = s.n_deg[0];
-        p.n_d2 = s.n_deg[1];
-        return p;
-    };
-    // the live instances' descriptors for one pass; returns its workgroup count
-    auto fill = [&](bool bind) {
-        unsigned wg = 0;
-        for (size_t x = 0; x < live.size(); x++) {
-            const Inst &s = t[live[x]];
-            SopTab p = describe(live[x]);
-            for (unsigned j = 0; bind && j < p.n_tables; j++) p.out[j] = s.work[j];
-            p.r_m = bind ? host_to_mont(s.ch) : 0;
-            p.first_wg = wg;
-            p.slot = (uint32_t)live[x];
-            h_desc[x] = p;
-            wg += (unsigned)product_wgs(s.len);
-        }
-        return wg;
-    };
-    // the round's coefficients of the instances in `who` from the published class sums; every transcript steps on a thread of its own
-    auto step = [&](const std::vector<size_t> &who) {
-        parallel_for(who.size(), [&](size_t x) {
-            Inst &s = t[who[x]];
-            uint64_t c[SOP_SUMS];
-            sop::coefficients(sh[who[x]].D, h_sums + SOP_SUMS * who[x], c);
-            s.ch = s.pr.step(c);
-        });
-    };
-    if (!live.empty()) {  // round 0: sums over the caller's tables
-        const unsigned wg = fill(false);
-        HIPCHK(ctx, hipMemcpyAsync(d_stage, h_desc, live.size() * sizeof(SopTab), hipMemcpyHostToDevice, ctx->stream));
-        const DoneFlag done = done_flag(ctx, 2);
-        launch_sop_sums(d_desc, (unsigned)live.size(), wg, d_part, ctx->stream);
-        launch_sop_finish(d_desc, (unsigned)live.size(), d_part, (uint64_t *)pin, ctx->stream, done);
-        HIPCHK(ctx, hipGetLastError());
-        CHK(wait_published(ctx, done));
-        step(live);
-    }
-    while (!live.empty()) {  // a later round: bind with the last challenge, sum the next round's terms
-        const unsigned wg = fill(true);
-        next.clear();
-        for (size_t i : live) {
-            Inst &s = t[i];
-            for (unsigned j = 0; j < sh[i].M; j++) s.cur[j] = s.work[j];
-            s.len /= 2;
-            if (s.len > HOST_TAIL_MAX) next.push_back(i);
-        }
-        HIPCHK(ctx, hipMemcpyAsync(d_stage, h_desc, live.size() * sizeof(SopTab), hipMemcpyHostToDevice, ctx->stream));
-        launch_sop_bind(d_desc, (unsigned)live.size(), wg, d_part, ctx->stream);
-        if (!next.empty()) {  // (an instance that is 1024 long now has its next round on the host: nobody reads its sums)
-            const DoneFlag done = done_flag(ctx, 2);
-            launch_sop_finish(d_desc, (unsigned)live.size(), d_part, (uint64_t *)pin, ctx->stream, done);
-            HIPCHK(ctx, hipGetLastError());
-            CHK(wait_published(ctx, done));
-            step(next);
-        } else {
-            HIPCHK(ctx, hipGetLastError());
-        }
-        live.swap(next);
-    }
-    // every instance's current tables in one hand-off
-    for (size_t i = 0; i < k; i++) {
-        SopTab p = describe(i);
-        p.tail_off = t[i].tail_off;
-        h_tdesc[i] = p;
-    }
-    HIPCHK(ctx, hipMemcpyAsync((void *)d_tdesc, h_tdesc, k * sizeof(SopTab), hipMemcpyHostToDevice, ctx->stream));
-    const DoneFlag done = done_flag(ctx, 2);
-    launch_sop_tails(d_tdesc, (unsigned)k, (uint32_t *)(pin + L.tail_off), ctx->stream, done);
-    HIPCHK(ctx, hipGetLastError());
-    CHK(wait_published(ctx, done));
-    const uint32_t *h_tail = (const uint32_t *)(pin + L.tail_off);
-    for (size_t x = 0; x < L.tail_words; x++)
-        if (h_tail[x] >= P) {  // (a device table is not checked on the way in)
-            set_err(ctx, "%s", NOT_CANONICAL_TEXT);
-            return ZIGZ_ERR_NOT_CANONICAL;
-        }
-    parallel_for(k, [&](size_t i) {
-        Inst &s = t[i];
-        std::vector<uint64_t> f[SOP_MAX_TABLES];
-        for (unsigned j = 0; j < sh[i].M; j++) f[j].assign(h_tail + s.tail_off + j * s.len, h_tail + s.tail_off + (j + 1) * s.len);
-        final_evals[i] = sop::tail_rounds(s.pr, f, sh[i].M, sh[i].terms, sh[i].T, table_evals + sh[i].moff);
-    });
-    for (const Inst &s : t)
-        if (s.pr.st != ZIGZ_OK) return s.pr.st;
-    return ZIGZ_OK;
+    Sop fam(a, table_evals, final_evals);
+    return sched::run(ctx, fam, a.k, d_tables, h_tables, a.ns, a.fixed, claimed_sums, rounds, points, bad_index);
     ZIGZ_NOTHROW_END(ctx)
 }
 
-// ---- verification: the oracles are the pools' entries, a table (one pair of the eval launch) or eq(tau, .) (host, closed form)
-zigz_status verify(zigz_ctx *ctx, const sop::VerifyArgs &a, bool host_tables, uint8_t *verdicts, uint64_t *expected_evals,
-                   uint64_t *oracle_evals, size_t *n_rejected, size_t *bad_index) {
-    ZIGZ_NOTHROW_BEGIN
-    const size_t k = a.k;
-    const bool reversed = (a.flags & ZIGZ_SUMCHECK_VERIFY_POINT_REVERSED) != 0;
-    const std::vector<sop::Shape> sh = sop::shapes(k, a.n_tables, a.ns, a.n_terms, a.term_degrees, a.term_tables, a.term_coeffs);
-    // per pool entry: its pair of the eval launch, or none (eq); per proof: its first tau word
-    std::vector<const void *> tabs;
-    std::vector<size_t> pair_ns, owner, pair_of, eoff(k + 1, 0);
-    std::vector<uint64_t> pair_points;
-    for (size_t i = 0; i < k; i++) {
-        size_t neq = 0;
-        for (unsigned j = 0; j < sh[i].M; j++) {
-            if (sop::kind_of(a, sh[i].moff + j) == pv::KIND_EQ) {
-                neq++;
-                pair_of.push_back((size_t)-1);
-                continue;
-            }
-            pair_of.push_back(tabs.size());
-            tabs.push_back(a.tables[sh[i].moff + j]);
-            pair_ns.push_back(a.ns[i]);
-            owner.push_back(i);
-            pair_points.insert(pair_points.end(), a.points + sh[i].voff, a.points + sh[i].voff + sh[i].nv);
+// the verifier's entry: a pool entry is a table or eq(tau, .), whose taus follow one another in eq_points
+struct SopVerify {
+    const sop::VerifyArgs &a;
+    const std::vector<sop::Shape> &sh;
+    std::vector<size_t> eoff;  // per proof: its first tau word
+
+    SopVerify(const sop::VerifyArgs &a, const std::vector<sop::Shape> &sh) : a(a), sh(sh), eoff(a.k + 1, 0) {
+        for (size_t i = 0; i < a.k; i++) {
+            size_t neq = 0;
+            for (unsigned j = 0; j < sh[i].M; j++) neq += !is_pair(sh[i].moff + j);
+            eoff[i + 1] = eoff[i] + neq * sh[i].nv;
         }
-        eoff[i + 1] = eoff[i] + neq * sh[i].nv;
     }
-    const size_t m = tabs.size(), entries = pair_of.size();
-    DoneFlag done;
-    const uint64_t *pairs = nullptr;
-    CHK(mle_eval_pairs_queue(ctx, tabs.data(), host_tables, pair_ns.data(), m, pair_points.data(), reversed, owner.data(), &pairs, &done,
-                             bad_index));
-    // the k replays and the eq entries, underneath the evaluation
-    std::vector<sv::Replay> rep(k);
-    std::vector<uint64_t> ev(entries, 0);
-    parallel_for(k, [&](size_t i) {
-        rep[i] = pv::replay_rounds(a.claimed_sums[i], a.rounds + sh[i].roff, sh[i].nv, sh[i].D);
+    bool is_pair(size_t e) const { return sop::kind_of(a, e) != pv::KIND_EQ; }
+    unsigned degree(size_t i) const { return sh[i].D; }
+    size_t roff(size_t i) const { return sh[i].roff; }
+    void host_values(size_t i, bool reversed, uint64_t *ev) const {
         const uint64_t *tau = a.eq_points ? a.eq_points + eoff[i] : nullptr;
         for (unsigned j = 0; j < sh[i].M; j++)
-            if (pair_of[sh[i].moff + j] == (size_t)-1) {
-                ev[sh[i].moff + j] = pv::eq_at(tau, a.points + sh[i].voff, sh[i].nv, reversed);
+            if (!is_pair(sh[i].moff + j)) {
+                ev[j] = pv::eq_at(tau, a.points + sh[i].voff, sh[i].nv, reversed);
                 tau += sh[i].nv;
             }
-    });
-    if (m) CHK(wait_published(ctx, done));
-    size_t rejected = 0;
-    for (size_t i = 0; i < k; i++) {
-        for (unsigned j = 0; j < sh[i].M; j++)
-            if (pair_of[sh[i].moff + j] != (size_t)-1) ev[sh[i].moff + j] = pairs[pair_of[sh[i].moff + j]];
-        const uint8_t ok = sop::verdict(rep[i], sh[i].terms, sh[i].T, ev.data() + sh[i].moff, sh[i].M, a.final_evals[i],
-                                        a.table_evals ? a.table_evals + sh[i].moff : nullptr);
-        rejected += !ok;
-        if (verdicts) verdicts[i] = ok;
-        if (expected_evals) expected_evals[i] = rep[i].expected;
     }
-    if (oracle_evals) memcpy(oracle_evals, ev.data(), entries * 8);
-    *n_rejected = rejected;
-    return ZIGZ_OK;
+    uint8_t verdict(size_t i, const sv::Replay &rep, const uint64_t *ev) const {
+        return sop::verdict(rep, sh[i].terms, sh[i].T, ev, sh[i].M, a.final_evals[i], a.table_evals ? a.table_evals + sh[i].moff : nullptr);
+    }
+};
+
+zigz_status verify(zigz_ctx *ctx, const sop::VerifyArgs &a, bool host_tables, uint8_t *verdicts, uint64_t *expected_evals,
+                   uint64_t *oracle_evals, size_t *n_rejected, size_t *bad_index) {
+    if (a.k == 0) {
+        *n_rejected = 0;
+        return ZIGZ_OK;
+    }
+    ZIGZ_NOTHROW_BEGIN
+    const std::vector<sop::Shape> sh = sop::shapes(a.k, a.n_tables, a.ns, a.n_terms, a.term_degrees, a.term_tables, a.term_coeffs);
+    SopVerify entry(a, sh);
+    return sched::verify_pool(ctx, a, sh, entry, host_tables, verdicts, expected_evals, oracle_evals, n_rejected, bad_index);
     ZIGZ_NOTHROW_END(ctx)
 }
 
@@ -311,10 +115,7 @@ extern "C" zigz_status zigz_sumcheck_prove_sop_batch(zigz_ctx *ctx, size_t k, co
     const sop::Args a{k, n_tables, (const void *const *)tables, ns, n_terms, term_degrees, term_tables, term_coeffs, fixed_challenges,
                       claimed_sums, rounds, points, table_evals, final_evals};
     ZIGZ_NOTHROW_BEGIN
-    bool value = false;
-    const zigz_status st = sop::check_sop_batch_host(a, bad_index, &value);
-    if (value) set_err(ctx, "%s", NOT_CANONICAL_TEXT);
-    CHK(st);
+    CHK(host_value_checks(ctx, [&](bool *value) { return sop::check_sop_batch_host(a, bad_index, value); }));
     ZIGZ_NOTHROW_END(ctx)
     return run(ctx, a, nullptr, tables, claimed_sums, rounds, points, table_evals, final_evals, bad_index);
 }
@@ -333,10 +134,6 @@ extern "C" zigz_status zigz_dev_sumcheck_verify_sop_batch(zigz_ctx *ctx, size_t 
     const sop::VerifyArgs a{k, n_tables, (const void *const *)d_tables, table_kinds, eq_points, ns, n_terms, term_degrees, term_tables,
                             term_coeffs, claimed_sums, rounds, points, table_evals, final_evals, flags, n_rejected};
     CHK(sop::check_verify_sop_batch(a, true, false, bad_index));
-    if (k == 0) {
-        *n_rejected = 0;
-        return ZIGZ_OK;
-    }
     return verify(ctx, a, false, verdicts, expected_evals, oracle_evals, n_rejected, bad_index);
 }
 
@@ -351,13 +148,6 @@ extern "C" zigz_status zigz_sumcheck_verify_sop_batch(zigz_ctx *ctx, size_t k, c
     if (!ctx) return ZIGZ_ERR_INVALID_ARGUMENT;
     const sop::VerifyArgs a{k, n_tables, (const void *const *)tables, table_kinds, eq_points, ns, n_terms, term_degrees, term_tables,
                             term_coeffs, claimed_sums, rounds, points, table_evals, final_evals, flags, n_rejected};
-    bool value = false;
-    const zigz_status st = sop::check_verify_sop_batch_host(a, bad_index, &value);
-    if (value) set_err(ctx, "%s", NOT_CANONICAL_TEXT);
-    CHK(st);
-    if (k == 0) {
-        *n_rejected = 0;
-        return ZIGZ_OK;
-    }
+    CHK(host_value_checks(ctx, [&](bool *value) { return sop::check_verify_sop_batch_host(a, bad_index, value); }));
     return verify(ctx, a, true, verdicts, expected_evals, oracle_evals, n_rejected, bad_index);
 }

@@ -3,7 +3,9 @@
 //   S_i = sum_x sum_{t < T_i} alpha_t prod_{j < d_t} pool[idx(t, j)](x)
 // over a pool of M_i tables.  Here: how the entries' flat arrays are laid out, their argument checks, the round coefficients from
 // the per-degree-class sums the kernels publish, the rounds of an instance whose tables have become small enough for the host --
-// SumcheckRounds::tail_rounds generalised to a pool with terms --, and the verifier's combination.  An instance's transcript and
+// SumcheckRounds::tail_rounds generalised to a pool with terms, with one body for these rounds and the zero-check's weighted ones
+// (tail_rounds_of) --, the verifying entries' argument walk, shared with zerocheck_host.hpp (verify_walk), and the verifier's
+// combination.  The prover's schedule and the verifier's run are product_schedule.hpp's.  An instance's transcript and
 // round step are sumcheck_host.hpp's, the replay and eq_at product_verify_host.hpp's.  Plain C++, no HIP: testable without a GPU
 // (tests/c_driver/sop_host.cpp).
 #include "product_host.hpp"
@@ -161,16 +163,25 @@ inline uint64_t combine(const Term *terms, unsigned T, const uint64_t *evals) {
 inline uint64_t mul(uint64_t a, uint64_t b) { return a * b % ZIGZ_BABYBEAR_P; }
 
 // SumcheckRounds::tail_rounds over a pool with terms: the last rounds on the remaining pool tables (pool[j]: m canonical values
-// each, bound in place), g(t) = sum_{i < m/2} sum_t alpha_t prod_j (a + t (b - a)) with a = pool[idx][i], b = pool[idx][i + m/2];
-// pr.ncoef is D + 1.  The tables, the coefficients and the challenges are canonical (checked on the way in), so mul() applies.
-// Writes every pool table fully bound (table_evals, when asked for) and returns combine() of them.
-inline uint64_t tail_rounds(SumcheckRounds &pr, std::vector<uint64_t> *pool, unsigned M, const Term *terms, unsigned T,
-                            uint64_t *table_evals = nullptr) {
+// each, bound in place), g(t) = sum_{i < m/2} w_i sum_t alpha_t prod_j (a + t (b - a)) with a = pool[idx][i], b = pool[idx][i + m/2].
+// The tables, the coefficients and the challenges are canonical (checked on the way in), so mul() applies.  Writes every pool
+// table fully bound (table_evals, when asked for) and returns combine() of them.  `wt` says what a pair weighs and how a round
+// steps: Unweighted below (w_i = 1, never multiplied in: the tail is where small instances spend their time), zc::Weighted.
+struct Unweighted {
+    static constexpr bool WEIGHTED = false;
+    std::vector<uint64_t> begin_round(size_t) { return {}; }
+    uint64_t step(SumcheckRounds &pr, const uint64_t *c) { return pr.step(c); }
+};
+template <class Wt>
+inline uint64_t tail_rounds_of(SumcheckRounds &pr, Wt &wt, std::vector<uint64_t> *pool, unsigned M, const Term *terms, unsigned T,
+                               uint64_t *table_evals) {
+    const unsigned D = pr.ncoef - (Wt::WEIGHTED ? 2 : 1);  // (the weighted rounds carry one coefficient more)
     for (size_t m = pool[0].size(); m > 1; m /= 2) {
         const size_t half = m / 2;
+        const std::vector<uint64_t> W = wt.begin_round(half);  // the pairs' weights, half of them (none: no weights)
         uint64_t c[MAX_DEGREE + 1] = {};
         for (size_t i = 0; i < half; i++) {
-            uint64_t a[MAX_TABLES], e[MAX_TABLES];
+            uint64_t a[MAX_TABLES], e[MAX_TABLES], u[MAX_DEGREE + 1] = {};  // u: the pair's own coefficients, where they are weighed
             for (unsigned j = 0; j < M; j++) {
                 a[j] = pool[j][i];
                 e[j] = f_sub(pool[j][i + half], a[j]);
@@ -183,10 +194,17 @@ inline uint64_t tail_rounds(SumcheckRounds &pr, std::vector<uint64_t> *pool, uns
                     for (unsigned x = j + 1; x > 0; x--) g[x] = f_add(mul(g[x], aj), mul(g[x - 1], ej));
                     g[0] = mul(g[0], aj);
                 }
-                for (unsigned j = 0; j <= tm.d; j++) c[j] = f_add(c[j], g[j]);
+                for (unsigned j = 0; j <= tm.d; j++) {
+                    if constexpr (Wt::WEIGHTED)
+                        u[j] = f_add(u[j], g[j]);
+                    else
+                        c[j] = f_add(c[j], g[j]);
+                }
             }
+            if constexpr (Wt::WEIGHTED)
+                for (unsigned j = 0; j <= D; j++) c[j] = f_add(c[j], mul(W[i], u[j]));
         }
-        const uint64_t ch = pr.step(c);
+        const uint64_t ch = wt.step(pr, c);
         if (pr.st != ZIGZ_OK) return 0;
         for (unsigned j = 0; j < M; j++) {  // partialEval's MSB-first bind, in place
             std::vector<uint64_t> &t = pool[j];
@@ -201,6 +219,12 @@ inline uint64_t tail_rounds(SumcheckRounds &pr, std::vector<uint64_t> *pool, uns
     if (table_evals)
         for (unsigned j = 0; j < M; j++) table_evals[j] = ev[j];
     return combine(terms, T, ev);
+}
+// the sop prover's: pr.ncoef is D + 1
+inline uint64_t tail_rounds(SumcheckRounds &pr, std::vector<uint64_t> *pool, unsigned M, const Term *terms, unsigned T,
+                            uint64_t *table_evals = nullptr) {
+    Unweighted wt;
+    return tail_rounds_of(pr, wt, pool, M, terms, T, table_evals);
 }
 
 // ------------------------------------------------------------------ verification
@@ -222,69 +246,86 @@ struct VerifyArgs {
 };
 inline uint8_t kind_of(const VerifyArgs &a, size_t entry) { return a.table_kinds ? a.table_kinds[entry] : pv::KIND_TABLE; }
 
-// What the entries say about their arguments before anything runs, as pv::check_verify_product_batch: ZIGZ_OK, or the status of
-// the first proof they reject, whose index goes to *bad_index.  Per proof, in order: the pool size, the term count, the terms; the
-// kinds (an unknown kind, an eq entry with a table pointer, an eq entry without eq_points); the prover's rule over the proof's
-// table entries and its point; then the words of the proof, of its coefficients and of its taus (ZIGZ_ERR_NOT_CANONICAL).
-inline zigz_status check_verify_sop_batch(const VerifyArgs &a, bool dev, bool values, size_t *bad_index) {
+// The per-proof walk of the verifying entries' checks (these and zerocheck_host.hpp's), over a VerifyArgs `a` of either: ZIGZ_OK,
+// or the status of the first proof it rejects, whose index goes to *bad_index.  Per proof, in order: the pool size, the term
+// count, the terms; the entries' kinds (entry(e): 1 a table, 0 a closed form, -1 ZIGZ_ERR_INVALID_ARGUMENT); the prover's rule
+// over the proof's table entries and its point; then the words of the proof -- D + extra_coef per round --, of its evals, of its
+// coefficients and whatever eq_words(i, v, closed forms of the proof) says of the family's taus (ZIGZ_ERR_NOT_CANONICAL).
+template <class A, class Entry, class EqWords>
+inline zigz_status verify_walk(const A &a, bool dev, bool values, unsigned extra_coef, size_t *bad_index, Entry entry, EqWords eq_words) {
     if (!a.n_rejected || (a.flags & ~(uint32_t)ZIGZ_SUMCHECK_VERIFY_POINT_REVERSED)) return ZIGZ_ERR_INVALID_ARGUMENT;
     if (a.k == 0) return ZIGZ_OK;
     if (a.k > ZIGZ_BATCH_MAX || !a.n_tables || !a.tables || !a.ns || !a.n_terms || !a.term_degrees || !a.term_tables || !a.term_coeffs ||
         !a.claimed_sums || !a.rounds || !a.points || !a.final_evals)
         return ZIGZ_ERR_INVALID_ARGUMENT;
     const TableRule rule{dev, values, true, true, sv::SV_MAX_LOG2_N};
-    size_t moff = 0, toff = 0, xoff = 0, voff = 0, roff = 0, eoff = 0;
+    size_t moff = 0, toff = 0, xoff = 0, voff = 0, roff = 0;
     for (size_t i = 0; i < a.k; i++) {
         const unsigned M = a.n_tables[i], T = a.n_terms[i];
         size_t nf = 0;
         zigz_status st = check_terms(M, T, a.term_degrees + toff, a.term_tables + xoff, &nf);
         if (st != ZIGZ_OK) return fail_at(bad_index, i, st);
         const void *tables[MAX_TABLES];
-        unsigned nt = 0, neq = 0, D = 0;
+        unsigned nt = 0, D = 0;
         for (unsigned j = 0; j < M; j++) {
-            const uint8_t kind = kind_of(a, moff + j);
-            if (kind == pv::KIND_TABLE) {
-                tables[nt++] = a.tables[moff + j];
-            } else if (kind != pv::KIND_EQ || a.tables[moff + j] || !a.eq_points) {
-                return fail_at(bad_index, i, ZIGZ_ERR_INVALID_ARGUMENT);
-            } else {
-                neq++;
-            }
+            const int kind = entry(moff + j);
+            if (kind < 0) return fail_at(bad_index, i, ZIGZ_ERR_INVALID_ARGUMENT);
+            if (kind) tables[nt++] = a.tables[moff + j];
         }
         st = table_rule(rule, tables, nt, a.ns[i], a.points + voff);
         if (st != ZIGZ_OK) return fail_at(bad_index, i, st);
         for (unsigned t = 0; t < T; t++)
             if (a.term_degrees[toff + t] > D) D = a.term_degrees[toff + t];
         const size_t v = log2_floor(a.ns[i]);
-        if (!canonical(a.rounds + roff, (D + 1) * v) || a.claimed_sums[i] >= ZIGZ_BABYBEAR_P || a.final_evals[i] >= ZIGZ_BABYBEAR_P ||
-            (a.table_evals && !canonical(a.table_evals + moff, M)) || !canonical(a.term_coeffs + toff, T) ||
-            (neq && !canonical(a.eq_points + eoff, neq * v)))
+        if (!canonical(a.rounds + roff, (D + extra_coef) * v) || a.claimed_sums[i] >= ZIGZ_BABYBEAR_P || a.final_evals[i] >= ZIGZ_BABYBEAR_P ||
+            (a.table_evals && !canonical(a.table_evals + moff, M)) || !canonical(a.term_coeffs + toff, T) || !eq_words(i, v, M - nt))
             return fail_at(bad_index, i, ZIGZ_ERR_NOT_CANONICAL);
         moff += M;
         toff += T;
         xoff += nf;
         voff += v;
-        roff += (D + 1) * v;
-        eoff += neq * v;
+        roff += (D + extra_coef) * v;
     }
     return ZIGZ_OK;
 }
-
-// The host form's checks in the family's order: a TABLE entry that holds a value >= p in a proof BEFORE the first one that fails
-// another check is reported instead, with its proof
-inline zigz_status check_verify_sop_batch_host(const VerifyArgs &a, size_t *bad_index, bool *value_found = nullptr) {
-    size_t bad = a.k;
-    const zigz_status st = check_verify_sop_batch(a, false, false, &bad);
+// The host forms' checks in the family's order, from the status `st` of the walk and the proof `bad` it stopped at: a TABLE entry
+// (is_table(e)) that holds a value >= p in a proof BEFORE the first one that fails another check is reported instead, with its proof
+template <class A, class IsTable>
+inline zigz_status verify_walk_host(const A &a, zigz_status st, size_t bad, size_t *bad_index, bool *value_found, IsTable is_table) {
     if (value_found) *value_found = false;
     if (st == ZIGZ_OK || bad >= a.k) return st;
     size_t moff = 0;
     for (size_t i = 0; i < bad; i++)  // (their pool sizes, kinds and pointers have passed)
         for (unsigned j = 0; j < a.n_tables[i]; j++, moff++)
-            if (kind_of(a, moff) == pv::KIND_TABLE && !canonical((const uint64_t *)a.tables[moff], a.ns[i])) {
+            if (is_table(moff) && !canonical((const uint64_t *)a.tables[moff], a.ns[i])) {
                 if (value_found) *value_found = true;
                 return fail_at(bad_index, i, ZIGZ_ERR_NOT_CANONICAL);
             }
     return fail_at(bad_index, bad, st);
+}
+
+// What zigz_[dev_]sumcheck_verify_sop_batch say about their arguments before anything runs, as pv::check_verify_product_batch:
+// verify_walk with D + 1 words per round; a kind is wrong when it is unknown, an eq entry with a table pointer, or an eq entry
+// without eq_points; a proof's taus are the next v words of eq_points per eq entry.
+inline zigz_status check_verify_sop_batch(const VerifyArgs &a, bool dev, bool values, size_t *bad_index) {
+    size_t eoff = 0;
+    return verify_walk(
+        a, dev, values, 1, bad_index,
+        [&](size_t e) {
+            const uint8_t kind = kind_of(a, e);
+            if (kind == pv::KIND_TABLE) return 1;
+            return kind != pv::KIND_EQ || a.tables[e] || !a.eq_points ? -1 : 0;
+        },
+        [&](size_t, size_t v, unsigned neq) {
+            if (neq && !canonical(a.eq_points + eoff, neq * v)) return false;
+            eoff += neq * v;
+            return true;
+        });
+}
+inline zigz_status check_verify_sop_batch_host(const VerifyArgs &a, size_t *bad_index, bool *value_found = nullptr) {
+    size_t bad = a.k;
+    const zigz_status st = check_verify_sop_batch(a, false, false, &bad);
+    return verify_walk_host(a, st, bad, bad_index, value_found, [&](size_t e) { return kind_of(a, e) == pv::KIND_TABLE; });
 }
 
 // the final check once the M pool entries' evaluations are known: their combination equals the last claim and final_eval, and

@@ -8,7 +8,8 @@
 //   t_r(X) = sum_{x < m/2} W_r[x] sum_t alpha_t prod_j (a_j[x] + X (b_j[x] - a_j[x])),   W_r = eq(tau_0 .. tau_{v-r-2}, .).
 // t_r has the degree D of C; s_r has D + 2 coefficients.  Here: the argument rules of the four entries, the prefix scalar P_r, the
 // multiplication by the linear factor, the weights the kernels read -- W_r[x] = lo[x & (2^L - 1)] hi_r[x >> L], lo the eq table of
-// tau_0..tau_{L-1} and hi_r the stages of eq(tau_L.., .) built by doubling --, the rounds of an instance that has become small
+// tau_0..tau_{L-1} and hi_r the stages of eq(tau_L.., .) built by doubling, their room per instance and the stage a pass reads
+// (weight_words, stage) --, the rounds of an instance that has become small
 // enough for the host, and the verifier's verdict.  On top of sop_host.hpp (layout, terms, class sums -> coefficients).  Plain
 // C++, no HIP: testable without a GPU (tests/c_driver/zerocheck_host.cpp).
 #include "sop_host.hpp"
@@ -49,6 +50,16 @@ inline uint32_t mont(uint64_t x) { return (uint32_t)f_mul(x, pd::R1); }
 // The round with 2^(L + s) pairs reads stage s.  words(v, L) words in all, fewer than 2^L + 2^(v - L).
 inline size_t stage_at(unsigned s) { return ((size_t)1 << s) - 1; }
 inline size_t hi_words(unsigned v, unsigned L) { return ((size_t)1 << (v - L)) - 1; }
+// A live instance's words in a call's weights region: lo and the stages of hi, rounded up so that the next instance's lo is
+// 16-byte aligned
+inline size_t weight_words(size_t n) { return ((size_t)1 << LOG2_LO) + (((size_t)1 << (log2_floor(n) - LOG2_LO)) + 3) / 4 * 4; }
+// A pass over tables of m values sums for the round with pairs(m, bind) index pairs -- m / 2 in round 0, m / 4 behind a bind -- and
+// reads stage log2(pairs) - LOG2_LO of hi (a bind at m == 2048 sums for nobody: stage 0, one valid word)
+inline size_t pairs(size_t m, bool bind) { return bind ? m / 4 : m / 2; }
+inline unsigned stage(size_t m, bool bind) {
+    const size_t p = pairs(m, bind);
+    return p >= ((size_t)1 << LOG2_LO) ? log2_floor(p) - LOG2_LO : 0;
+}
 inline void build_weights(const uint64_t *tau, unsigned v, unsigned L, uint32_t *lo, uint32_t *hi) {
     const std::vector<uint64_t> e = eq_prefix(tau, L);
     for (size_t x = 0; x < e.size(); x++) lo[x] = mont(e[x]);
@@ -91,49 +102,19 @@ struct Weight {
     }
 };
 
-// sop::tail_rounds under the weight: the last rounds on the remaining pool tables (pool[j]: m canonical values each, bound in
-// place), t_r from W_r built afresh for every round (m / 2 words); pr.ncoef is D + 2 and pr.round the rounds already run.
-// Writes every pool table fully bound (table_evals, when asked for) and returns sop::combine() of them -- C at the point, WITHOUT
-// the eq factor.
+// sop::tail_rounds under the weight: t_r from W_r built afresh for every round (m / 2 words); pr.ncoef is D + 2 and pr.round the
+// rounds already run.  Returns sop::combine() of the fully bound tables -- C at the point, WITHOUT the eq factor.
+struct Weighted {
+    static constexpr bool WEIGHTED = true;
+    Weight &w;
+    unsigned D;
+    std::vector<uint64_t> begin_round(size_t half) { return eq_prefix(w.tau, log2_floor(half)); }
+    uint64_t step(SumcheckRounds &pr, const uint64_t *c) { return w.step(pr, D, c); }
+};
 inline uint64_t tail_rounds(SumcheckRounds &pr, Weight &w, std::vector<uint64_t> *pool, unsigned M, const sop::Term *terms, unsigned T,
                             unsigned D, uint64_t *table_evals = nullptr) {
-    for (size_t m = pool[0].size(); m > 1; m /= 2) {
-        const size_t half = m / 2;
-        const std::vector<uint64_t> W = eq_prefix(w.tau, log2_floor(half));
-        uint64_t c[sop::MAX_DEGREE + 1] = {};
-        for (size_t i = 0; i < half; i++) {
-            uint64_t a[sop::MAX_TABLES], e[sop::MAX_TABLES], u[sop::MAX_DEGREE + 1] = {};
-            for (unsigned j = 0; j < M; j++) {
-                a[j] = pool[j][i];
-                e[j] = f_sub(pool[j][i + half], a[j]);
-            }
-            for (unsigned t = 0; t < T; t++) {
-                const sop::Term &tm = terms[t];
-                uint64_t g[sop::MAX_DEGREE + 1] = {sop::mul(tm.alpha, a[tm.idx[0]]), sop::mul(tm.alpha, e[tm.idx[0]]), 0, 0};
-                for (unsigned j = 1; j < tm.d; j++) {  // g *= a + e t
-                    const uint64_t aj = a[tm.idx[j]], ej = e[tm.idx[j]];
-                    for (unsigned x = j + 1; x > 0; x--) g[x] = f_add(sop::mul(g[x], aj), sop::mul(g[x - 1], ej));
-                    g[0] = sop::mul(g[0], aj);
-                }
-                for (unsigned j = 0; j <= tm.d; j++) u[j] = f_add(u[j], g[j]);
-            }
-            for (unsigned j = 0; j <= D; j++) c[j] = f_add(c[j], sop::mul(W[i], u[j]));
-        }
-        const uint64_t ch = w.step(pr, D, c);
-        if (pr.st != ZIGZ_OK) return 0;
-        for (unsigned j = 0; j < M; j++) {  // partialEval's MSB-first bind, in place
-            std::vector<uint64_t> &t = pool[j];
-            for (size_t x = 0; x < half; x++) t[x] = f_add(t[x], sop::mul(ch, f_sub(t[x + half], t[x])));
-            t.resize(half);
-        }
-    }
-    if (pr.round != pr.nv) pr.st = ZIGZ_ERR_PROTOCOL_ERROR;
-    if (pool[0].empty()) return 0;
-    uint64_t ev[sop::MAX_TABLES];
-    for (unsigned j = 0; j < M; j++) ev[j] = pool[j][0];
-    if (table_evals)
-        for (unsigned j = 0; j < M; j++) table_evals[j] = ev[j];
-    return sop::combine(terms, T, ev);
+    Weighted wt{w, D};
+    return sop::tail_rounds_of(pr, wt, pool, M, terms, T, table_evals);
 }
 
 // ------------------------------------------------------------------ the prover's arguments
@@ -221,56 +202,23 @@ struct VerifyArgs {
     const size_t *n_rejected;
 };
 
-// What the entries say about their arguments before anything runs, as sop::check_verify_sop_batch: per proof, in order, the pool
-// size, the term count, the terms; the prover's rule over the proof's tables and its point; then the words of the proof (D_i + 2
-// per round), of its coefficients and of its tau (ZIGZ_ERR_NOT_CANONICAL).
+// What the entries say about their arguments before anything runs: sop::verify_walk with D_i + 2 words per round, every pool
+// entry a table, eq_points required, and a proof's tau (its v words of eq_points) and eq_eval canonical.
 inline zigz_status check_verify_zerocheck_batch(const VerifyArgs &a, bool dev, bool values, size_t *bad_index) {
-    if (!a.n_rejected || (a.flags & ~(uint32_t)ZIGZ_SUMCHECK_VERIFY_POINT_REVERSED)) return ZIGZ_ERR_INVALID_ARGUMENT;
-    if (a.k == 0) return ZIGZ_OK;
-    if (a.k > ZIGZ_BATCH_MAX || !a.n_tables || !a.tables || !a.eq_points || !a.ns || !a.n_terms || !a.term_degrees || !a.term_tables ||
-        !a.term_coeffs || !a.claimed_sums || !a.rounds || !a.points || !a.final_evals)
-        return ZIGZ_ERR_INVALID_ARGUMENT;
-    const TableRule rule{dev, values, true, true, sv::SV_MAX_LOG2_N};
-    size_t moff = 0, toff = 0, xoff = 0, voff = 0, roff = 0;
-    for (size_t i = 0; i < a.k; i++) {
-        const unsigned M = a.n_tables[i], T = a.n_terms[i];
-        size_t nf = 0;
-        zigz_status st = sop::check_terms(M, T, a.term_degrees + toff, a.term_tables + xoff, &nf);
-        if (st != ZIGZ_OK) return fail_at(bad_index, i, st);
-        st = table_rule(rule, a.tables + moff, M, a.ns[i], a.points + voff);
-        if (st != ZIGZ_OK) return fail_at(bad_index, i, st);
-        unsigned D = 0;
-        for (unsigned t = 0; t < T; t++)
-            if (a.term_degrees[toff + t] > D) D = a.term_degrees[toff + t];
-        const size_t v = log2_floor(a.ns[i]);
-        if (!canonical(a.rounds + roff, (D + 2) * v) || a.claimed_sums[i] >= ZIGZ_BABYBEAR_P || a.final_evals[i] >= ZIGZ_BABYBEAR_P ||
-            (a.table_evals && !canonical(a.table_evals + moff, M)) || (a.eq_evals && a.eq_evals[i] >= ZIGZ_BABYBEAR_P) ||
-            !canonical(a.term_coeffs + toff, T) || !canonical(a.eq_points + voff, v))
-            return fail_at(bad_index, i, ZIGZ_ERR_NOT_CANONICAL);
-        moff += M;
-        toff += T;
-        xoff += nf;
-        voff += v;
-        roff += (D + 2) * v;
-    }
-    return ZIGZ_OK;
+    if (a.k && !a.eq_points) return ZIGZ_ERR_INVALID_ARGUMENT;  // (as every other failure in front of the proofs)
+    size_t voff = 0;
+    return sop::verify_walk(
+        a, dev, values, 2, bad_index, [](size_t) { return 1; },
+        [&](size_t i, size_t v, unsigned) {
+            if ((a.eq_evals && a.eq_evals[i] >= ZIGZ_BABYBEAR_P) || !canonical(a.eq_points + voff, v)) return false;
+            voff += v;
+            return true;
+        });
 }
-
-// The host form's checks in the family's order: a table that holds a value >= p in a proof BEFORE the first one that fails
-// another check is reported instead, with its proof
 inline zigz_status check_verify_zerocheck_batch_host(const VerifyArgs &a, size_t *bad_index, bool *value_found = nullptr) {
     size_t bad = a.k;
     const zigz_status st = check_verify_zerocheck_batch(a, false, false, &bad);
-    if (value_found) *value_found = false;
-    if (st == ZIGZ_OK || bad >= a.k) return st;
-    size_t moff = 0;
-    for (size_t i = 0; i < bad; i++)  // (their pool sizes and pointers have passed)
-        for (unsigned j = 0; j < a.n_tables[i]; j++, moff++)
-            if (!canonical((const uint64_t *)a.tables[moff], a.ns[i])) {
-                if (value_found) *value_found = true;
-                return fail_at(bad_index, i, ZIGZ_ERR_NOT_CANONICAL);
-            }
-    return fail_at(bad_index, bad, st);
+    return sop::verify_walk_host(a, st, bad, bad_index, value_found, [](size_t) { return true; });
 }
 
 // the final check once the M tables' evaluations and eq's are known: eq * C(oracles) equals the last claim and final_eval, and
