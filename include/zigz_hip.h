@@ -845,6 +845,87 @@ zigz_status zigz_sumcheck_verify_zerocheck_batch(zigz_ctx *ctx, size_t k, const 
                                                  uint32_t flags, uint8_t *verdicts, uint64_t *expected_evals, uint64_t *oracle_evals,
                                                  size_t *n_rejected, size_t *bad_index);
 
+/* k independent PRODUCT TREES: column i holds n = ns[i] = 2^v canonical words, V_v = column, V_j[x] = V_{j+1}[x] * V_{j+1}[x + 2^j]
+ * for x < 2^j (the HALVES pairing: it matches the MSB-first bind of the sumchecks, and the two operands of a layer are contiguous
+ * sub-arrays), down to V_0[0] = the product of all n words.  d_out[i]: ns[i] packed u32 words, 16-byte aligned; layer j (2^j
+ * canonical words) sits at word ns[i] - 2^(j+1) for j = v - 1 .. 0, so every layer of 4 words or more is 16-byte aligned and the
+ * product is word ns[i] - 2; word ns[i] - 1 is not written and nothing behind the buffer is.  The layers above 2048 words are
+ * computed by passes of up to three fused levels, one launch per pass for all columns (about 4 n bytes read and 3.5 n written
+ * per pass); the rest by one workgroup per column.  The call is queued on the context's stream and does not wait, like
+ * zigz_dev_eq_table_batch.  The columns are only read (and not checked: a word >= p gives an unspecified canonical product).
+ * Every argument is checked for every column before anything is launched or written; the first failing column's index goes to
+ * *bad_index (if non-NULL): ZIGZ_ERR_INVALID_ARGUMENT for ctx or an array NULL, k > ZIGZ_BATCH_MAX, a column or output that is
+ * NULL or not 16-byte aligned, ns[i] > 2^ZIGZ_PRODUCT_MAX_LOG2_N, columns longer than 2048 that together make 2^24 chunks of 8192
+ * words or more; ZIGZ_ERR_EMPTY_EVALUATIONS / ZIGZ_ERR_LENGTH_NOT_POWER_OF_TWO for the shape; ZIGZ_ERR_NO_VARIABLES for
+ * ns[i] == 1.  k == 0 returns ZIGZ_OK and touches nothing. */
+zigz_status zigz_dev_product_layers_batch(zigz_ctx *ctx, size_t k, const uint32_t *const *d_tables, const size_t *ns,
+                                          uint32_t *const *d_out, size_t *bad_index);
+/* host columns (canonical u64, ZIGZ_ERR_NOT_CANONICAL with the column's index otherwise), narrowed and uploaded in one copy;
+ * out[i]: ns[i] u64 words in the same layout (word ns[i] - 1 is not written).  Waits for the trees. */
+zigz_status zigz_product_layers_batch(zigz_ctx *ctx, size_t k, const uint64_t *const *tables, const size_t *ns, uint64_t *const *out,
+                                      size_t *bad_index);
+
+/* k independent GRAND-PRODUCT arguments (the layered, GKR-style product tree): instance i proves that products[i] is the product
+ * of the n = ns[i] = 2^v words of its column A.  With the tree above, L_j = V_{j+1}[0 : 2^j] and H_j = V_{j+1}[2^j : 2^(j+1)].
+ * Points are in Multilinear.eval's convention throughout (coordinate 0 goes with the LSB of the index).  Per instance ONE
+ * transcript, fresh at the start, used in this order:
+ *   1. absorb products[i];
+ *   2. layer 0: l_0 = V_1[0], h_0 = V_1[1]; absorb l_0, h_0; draw c_0; tau^(1) = (c_0), claim_1 = l_0 + c_0 (h_0 - l_0);
+ *   3. layer j = 1 .. v - 1: the closed-form zero-check (zigz_dev_sumcheck_prove_zerocheck_batch with the pool (L_j, H_j), the
+ *      one term L_j * H_j and tau^(j)) of sum_x eq(tau^(j), x) L_j(x) H_j(x) = claim_j: j rounds of 4 coefficients, each absorbed
+ *      and then drawn from as there; with q the round challenges reversed, l_j = L_j(q), h_j = H_j(q); absorb l_j, h_j; draw c_j;
+ *      tau^(j+1) = (q_0, .., q_{j-1}, c_j), claim_(j+1) = l_j + c_j (h_j - l_j);
+ *   4. leaf_point = tau^(v), leaf_eval = claim_v, which equals A(leaf_point) for an honest prover.
+ * Outputs, concatenated in instance order: products (1 word per instance), layer_evals (2 v: l_j, h_j for j = 0 .. v - 1), rounds
+ * (2 v (v - 1): layer by layer, each round c_0..c_3), points (v (v - 1) / 2: layer by layer, in round order), layer_challenges
+ * (v), leaf_points (v), leaf_evals (1).  fixed_challenges != NULL is the interactive form: v (v + 1) / 2 words per instance in
+ * order of use (c_0, layer 1's round challenge, c_1, layer 2's two, c_2, ...), no transcript.
+ * Schedule: the trees of all instances are built into a workspace (ns[i] words each; the leaf layer is the caller's column, which
+ * is only read) and the top of every tree -- the layers of at most 2048 words -- is handed to the host ONCE; the host runs layer
+ * 0 and the layers whose tables are at most 1024 long for all instances in parallel; then, for j = 11 .. max v - 1, ONE run of
+ * the zero-check schedule serves layer j of every instance with v_i > j.
+ * Every argument is checked for every instance before anything is launched or written, with zigz_dev_product_layers_batch's
+ * statuses in its order; then, per instance, ZIGZ_ERR_NOT_CANONICAL for a fixed challenge >= p; an output array NULL is
+ * ZIGZ_ERR_INVALID_ARGUMENT.  The column on the device is not checked on the way in; a value >= p that reaches the host is
+ * ZIGZ_ERR_NOT_CANONICAL.  k == 0 returns ZIGZ_OK and touches nothing. */
+zigz_status zigz_dev_grand_product_prove_batch(zigz_ctx *ctx, size_t k, const uint32_t *const *d_tables, const size_t *ns,
+                                               const uint64_t *fixed_challenges, uint64_t *products, uint64_t *layer_evals,
+                                               uint64_t *rounds, uint64_t *points, uint64_t *layer_challenges, uint64_t *leaf_points,
+                                               uint64_t *leaf_evals, size_t *bad_index);
+/* host columns (canonical u64, ZIGZ_ERR_NOT_CANONICAL with the instance's index otherwise), narrowed and uploaded in one copy */
+zigz_status zigz_grand_product_prove_batch(zigz_ctx *ctx, size_t k, const uint64_t *const *tables, const size_t *ns,
+                                           const uint64_t *fixed_challenges, uint64_t *products, uint64_t *layer_evals, uint64_t *rounds,
+                                           uint64_t *points, uint64_t *layer_challenges, uint64_t *leaf_points, uint64_t *leaf_evals,
+                                           size_t *bad_index);
+
+/* k independent verifications of the Fiat-Shamir proofs zigz_dev_grand_product_prove_batch writes, in its layout.  Every
+ * challenge is derived here, from one transcript per proof: l_0 h_0 == products[i]; per layer j >= 1 the claim chain (g(0) +
+ * g(1) == claim, absorb, draw, claim = g(challenge)) and eq(tau^(j), q) l_j h_j == the last claim; the derived leaf point must
+ * equal leaf_points, leaf_evals[i] must equal claim_v, and so must the column's evaluation A(leaf_points[i]) -- queued for all
+ * proofs in the batched eval's launch FIRST, while the host's threads replay the layers.
+ * ZIGZ_GRAND_PRODUCT_LEAF_DEFERRED is for a caller that holds a commitment, not the column: d_tables must be NULL, nothing is
+ * launched, and a proof is accepted iff the layers hold, the leaf point is the derived one and leaf_evals[i] == claim_v;
+ * A(leaf_point) == leaf_evals[i] is then the CALLER'S check, for example through zigz_commit_open.
+ * Outputs: verdicts[k] (may be NULL); *n_rejected; expected_evals[k] (may be NULL) the claim at the failing step -- the product
+ * check, a round, a layer's final check -- or claim_v; oracle_evals[k] (may be NULL; not written with the flag) the column's
+ * evaluation at leaf_points[i].
+ * Statuses are for the shape of the arguments only, checked for every proof before anything is launched or written; the first
+ * failing proof's index goes to *bad_index (if non-NULL): ZIGZ_ERR_INVALID_ARGUMENT for ctx or n_rejected NULL, an unknown flag, a
+ * NULL input array when k > 0, columns given with the flag or missing without it, k > ZIGZ_BATCH_MAX, a column that is NULL or not
+ * 16-byte aligned, ns[i] > 2^ZIGZ_PRODUCT_MAX_LOG2_N; the prover's rules for the shape (ns[i] == 1 is ZIGZ_ERR_NO_VARIABLES);
+ * ZIGZ_ERR_NOT_CANONICAL for any word of a proof >= p.  k == 0: ZIGZ_OK, *n_rejected = 0, nothing else touched. */
+#define ZIGZ_GRAND_PRODUCT_LEAF_DEFERRED 1u
+zigz_status zigz_dev_grand_product_verify_batch(zigz_ctx *ctx, size_t k, const uint32_t *const *d_tables, const size_t *ns,
+                                                const uint64_t *products, const uint64_t *layer_evals, const uint64_t *rounds,
+                                                const uint64_t *leaf_points, const uint64_t *leaf_evals, uint32_t flags,
+                                                uint8_t *verdicts, uint64_t *expected_evals, uint64_t *oracle_evals, size_t *n_rejected,
+                                                size_t *bad_index);
+/* host columns (canonical u64, ZIGZ_ERR_NOT_CANONICAL with the proof's index otherwise), narrowed and uploaded in one copy */
+zigz_status zigz_grand_product_verify_batch(zigz_ctx *ctx, size_t k, const uint64_t *const *tables, const size_t *ns,
+                                            const uint64_t *products, const uint64_t *layer_evals, const uint64_t *rounds,
+                                            const uint64_t *leaf_points, const uint64_t *leaf_evals, uint32_t flags, uint8_t *verdicts,
+                                            uint64_t *expected_evals, uint64_t *oracle_evals, size_t *n_rejected, size_t *bad_index);
+
 /* ---------------------------------------------------------------- host SHA3 sponge / transcript
  * FiatShamirTranscript   src/core/hash.zig:255-324 (sequential by construction: stays on the host) */
 zigz_transcript *zigz_transcript_new(void);

@@ -191,6 +191,15 @@ SIGNATURES = {
     "zigz_sumcheck_verify_zerocheck_batch": (C.c_int32, [vp, C.c_size_t, C.POINTER(C.c_uint), C.POINTER(u64p), u64p, szp,
                                                          C.POINTER(C.c_uint), C.POINTER(C.c_uint), u8p, u64p, u64p, u64p, u64p, u64p, u64p,
                                                          u64p, C.c_uint32, u8p, u64p, u64p, szp, szp]),
+    "zigz_dev_product_layers_batch": (C.c_int32, [vp, C.c_size_t, C.POINTER(vp), szp, C.POINTER(vp), szp]),
+    "zigz_product_layers_batch": (C.c_int32, [vp, C.c_size_t, C.POINTER(u64p), szp, C.POINTER(u64p), szp]),
+    "zigz_dev_grand_product_prove_batch": (C.c_int32, [vp, C.c_size_t, C.POINTER(vp), szp, u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p,
+                                                       szp]),
+    "zigz_grand_product_prove_batch": (C.c_int32, [vp, C.c_size_t, C.POINTER(u64p), szp, u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p, szp]),
+    "zigz_dev_grand_product_verify_batch": (C.c_int32, [vp, C.c_size_t, C.POINTER(vp), szp, u64p, u64p, u64p, u64p, u64p, C.c_uint32, u8p,
+                                                        u64p, u64p, szp, szp]),
+    "zigz_grand_product_verify_batch": (C.c_int32, [vp, C.c_size_t, C.POINTER(u64p), szp, u64p, u64p, u64p, u64p, u64p, C.c_uint32, u8p, u64p,
+                                                    u64p, szp, szp]),
     "zigz_sumcheck_radix_run_batch": (C.c_int32, [vp, RB_BLOCK_SUMS_FN, RB_FOLD_FN, RB_READ_TAIL_FN, C.c_size_t, szp, u64p, u64p, u64p,
                                                   u64p]),
     "zigz_dev_sumcheck_prove_rccl": (C.c_int32, [vp, vp, C.c_size_t, vp, u64p, u64p, u64p]),

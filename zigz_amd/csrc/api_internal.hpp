@@ -2,7 +2,7 @@
 // Shared by the translation units behind the C ABI of libzigz_hip.so (include/zigz_hip.h) -- api.cpp (contexts, workspaces,
 // boundary conversion, transcript), api_mle.cpp (MLE ops, the GPU passes of the sumcheck), api_commit.cpp (Merkle trees, commit
 // jobs), api_misc.cpp (Lasso, the measurement hook), api_batch.cpp, api_merkle_batch.cpp, api_merkle_verify.cpp,
-// api_mle_batch.cpp, api_product.cpp, api_sop.cpp, api_zerocheck.cpp (the batched entries; the last three share the round schedule
+// api_mle_batch.cpp, api_product.cpp, api_sop.cpp, api_zerocheck.cpp, api_grand_product.cpp (the batched entries; the last four share the round schedule
 // and the pool verifier of product_schedule.hpp): the context, its workspaces, the error macros and the helpers one unit needs
 // from another.  What needs no HIP lives in headers of its own, testable without a GPU: the host side of every
 // sumcheck in sumcheck_host.hpp (field helpers, argument rule, round step, tail rounds, radix schedules), the plans in
@@ -30,7 +30,7 @@
 using namespace zk;
 
 // ------------------------------------------------------------------ context
-enum { WS_IN64 = 0, WS_IN32, WS_OUT32, WS_OUT64, WS_SCRATCH, WS_TREE, WS_FOLD, WS_MISC, WS_COLS, WS_LASSO, WS_DEDUP, WS_WITNESS, WS_RUNS, WS_RUNMETA, WS_CONS, WS_CONSMETA, WS_BATCH, WS_SCBATCH, WS_SCBATCH_IN, WS_VERIFY, WS_OPEN, WS_MLEBATCH, WS_MLEBATCH_PART, WS_MLEBATCH_IN, WS_PRODUCT, WS_PRODUCT_WORK, WS_PRODUCT_IN, WS_EQ, WS_EQ_OUT, WS_SLOTS };
+enum { WS_IN64 = 0, WS_IN32, WS_OUT32, WS_OUT64, WS_SCRATCH, WS_TREE, WS_FOLD, WS_MISC, WS_COLS, WS_LASSO, WS_DEDUP, WS_WITNESS, WS_RUNS, WS_RUNMETA, WS_CONS, WS_CONSMETA, WS_BATCH, WS_SCBATCH, WS_SCBATCH_IN, WS_VERIFY, WS_OPEN, WS_MLEBATCH, WS_MLEBATCH_PART, WS_MLEBATCH_IN, WS_PRODUCT, WS_PRODUCT_WORK, WS_PRODUCT_IN, WS_EQ, WS_EQ_OUT, WS_GP, WS_GP_TREE, WS_GP_IN, WS_SLOTS };
 
 constexpr int KEV_MAX = 72;
 struct zigz_ctx {

@@ -684,4 +684,33 @@ struct ZcWeights {
 void launch_zc_sums(const SopTab *d_tabs, const ZcWeights *d_w, unsigned nt, unsigned nwg, unsigned long long *d_part, hipStream_t s);
 void launch_zc_bind(const SopTab *d_tabs, const ZcWeights *d_w, unsigned nt, unsigned nwg, unsigned long long *d_part, hipStream_t s);
 
+// ---- product trees of the grand-product argument (grand_product.hip): V_j[x] = V_{j+1}[x] * V_{j+1}[x + 2^j] for k
+// independent columns.  A tree buffer of a column of n = 2^v words holds the layers v - 1 .. 0, layer j at word n - 2^(j+1)
+// (grand_product_host.hpp: layer_at); word n - 1 is never written.  The layers above 2048 words are computed by passes of up to
+// three fused levels each (k_gp_layers), one launch per pass for all columns; the rest by one workgroup per column through LDS
+// (k_gp_top), which can also hand the top of every tree to the host.
+constexpr unsigned GP_CHUNK = 8192;   // words of the layer a pass reads that one workgroup owns
+constexpr unsigned GP_TOP_LOG2 = 11;  // gp::TOP_LOG2: k_gp_top starts at the first layer of at most 2048 words
+struct GpTab {  // one column in one pass; its workgroups are [first_wg, first_wg of column j + 1)
+    const uint32_t *in;  // layer J: the caller's column (J == v) or the layer in the tree buffer; 2^J packed canonical words, 16-byte aligned
+    uint32_t *tree;      // the tree buffer (n words, 16-byte aligned)
+    uint64_t n;          // the column's length
+    uint32_t log2_in;    // J > GP_TOP_LOG2
+    uint32_t levels;     // 1..3, J - levels >= GP_TOP_LOG2: the pass writes the layers J - 1 .. J - levels
+    uint32_t first_wg;
+    uint32_t reserved;
+};
+inline size_t gp_wgs(size_t m) { return (m + GP_CHUNK - 1) / GP_CHUNK; }
+void launch_gp_layers(const GpTab *d_tabs, unsigned nt, unsigned nwg, hipStream_t s);
+struct GpTop {  // one column's top: from layer log2_in (<= GP_TOP_LOG2) at `in` down to layer 0
+    const uint32_t *in;
+    uint32_t *tree;
+    uint64_t n;
+    uint64_t top_off;  // hand-off: first word of the column's 2^(log2_in + 1) words -- layer j at 2^(log2_in + 1) - 2^(j+1), the last unused
+    uint32_t log2_in;
+    uint32_t reserved;
+};
+// h_dst == nullptr: the trees alone, nothing signalled; otherwise the top layers go to pinned memory as well and `done` is signalled
+void launch_gp_top(const GpTop *d_tabs, unsigned nt, uint32_t *h_dst, hipStream_t s, DoneFlag done);
+
 }  // namespace zk

@@ -82,10 +82,13 @@ zigz_status plan(const F &fam, size_t k, const size_t *ns, bool host_tables, Lay
     return ZIGZ_OK;
 }
 
-// d_tables or h_tables: every instance's tables one behind the other, on the device or on the host
+// d_tables or h_tables: every instance's tables one behind the other, on the device or on the host.  transcripts (k of them, or
+// none: a fresh one per instance): the transcript instance i starts from, handed back as its last round left it -- a caller
+// whose proof runs through several calls (api_grand_product.cpp: one call per layer) carries it from one to the next
 template <class F>
 zigz_status run(zigz_ctx *ctx, F &fam, size_t k, const uint32_t *const *d_tables, const uint64_t *const *h_tables, const size_t *ns,
-                const uint64_t *fixed, uint64_t *claimed_sums, uint64_t *rounds, uint64_t *points, size_t *bad_index) {
+                const uint64_t *fixed, uint64_t *claimed_sums, uint64_t *rounds, uint64_t *points, size_t *bad_index,
+                Transcript *transcripts = nullptr) {
     using Tab = typename F::Tab;
     ZIGZ_NOTHROW_BEGIN
     Layout L;
@@ -131,6 +134,7 @@ zigz_status run(zigz_ctx *ctx, F &fam, size_t k, const uint32_t *const *d_tables
             s.pr.rounds = rounds + roff;
             s.pr.point = points + voff;
             s.pr.fixed = fixed ? fixed + voff : nullptr;
+            if (transcripts) s.pr.tr = transcripts[i];
             foff += M;
             voff += s.pr.nv;
             roff += (size_t)s.pr.ncoef * s.pr.nv;
@@ -233,6 +237,7 @@ zigz_status run(zigz_ctx *ctx, F &fam, size_t k, const uint32_t *const *d_tables
     });
     for (const auto &s : t)
         if (s.pr.st != ZIGZ_OK) return s.pr.st;
+    for (size_t i = 0; transcripts && i < k; i++) transcripts[i] = t[i].pr.tr;
     return ZIGZ_OK;
     ZIGZ_NOTHROW_END(ctx)
 }

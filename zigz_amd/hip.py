@@ -24,6 +24,7 @@ TRACE_STEP32_DTYPE = np.dtype([("pc", "<u8"), ("rd_value", "<u8"), ("imm", "<i4"
 MEM_ACCESS_DTYPE = np.dtype([("addr", "<u8"), ("value", "<u8")])
 assert TRACE_STEP32_DTYPE.itemsize == 32 and MEM_ACCESS_DTYPE.itemsize == 16
 NO_MEM_ACCESS = 0xFFFFFFFF
+GRAND_PRODUCT_LEAF_DEFERRED = 1  # ZIGZ_GRAND_PRODUCT_LEAF_DEFERRED: no column; A(leaf_point) == leaf_eval is the caller's check
 SUMCHECK_VERIFY_POINT_REVERSED = 1  # ZIGZ_SUMCHECK_VERIFY_POINT_REVERSED: the oracle at the reversed point (honest proofs accept)
 
 
@@ -778,6 +779,97 @@ class Context:
         return self._verify_zerocheck_batch(lib.zigz_dev_sumcheck_verify_zerocheck_batch, ptrs,
                                             [len(tables) for tables, _, _ in d_instances], [terms for _, terms, _ in d_instances],
                                             [tau for _, _, tau in d_instances], ns, proofs, flags, check_table_evals, check_eq_evals)
+
+    # ---- product trees and the grand-product argument
+    def product_layers_batch(self, tables):
+        """zigz_product_layers_batch: for every column (2^v canonical words) its product tree as one np.uint64 array of n words --
+        layer j (2^j words) at word n - 2^(j+1), j = v - 1 .. 0, the product at word n - 2; word n - 1 is not written (left 0)."""
+        k = len(tables)
+        arrs = [_u64(t) for t in tables]
+        ns = (C.c_size_t * max(k, 1))(*[len(t) for t in tables])
+        ptrs = (u64p * max(k, 1))(*[p for _, p in arrs])
+        outs = [_out_u64(len(t)) for t in tables]
+        optrs = (u64p * max(k, 1))(*[p for _, p in outs])
+        bad = C.c_size_t(0)
+        self.check_batch(lib.zigz_product_layers_batch(self.h, k, ptrs, ns, optrs, C.byref(bad)), bad)
+        return [o[:len(t)] for (o, _), t in zip(outs, tables)]
+
+    def dev_product_layers_batch(self, d_tables, ns, d_out):
+        """zigz_dev_product_layers_batch: device columns (packed u32 canonical, 16-byte aligned; only read) into device buffers of
+        ns[i] u32 words each (addresses, 16-byte aligned): queued on the context's stream, not waited for."""
+        k = len(ns)
+        nsa = (C.c_size_t * max(k, 1))(*[int(n) for n in ns])
+        ptrs = (vp * max(k, 1))(*[int(d) for d in d_tables])
+        optrs = (vp * max(k, 1))(*[int(d) for d in d_out])
+        bad = C.c_size_t(0)
+        self.check_batch(lib.zigz_dev_product_layers_batch(self.h, k, ptrs, nsa, optrs, C.byref(bad)), bad)
+
+    def _grand_product_prove(self, fn, ptrs, ns, challenges):
+        k = len(ns)
+        vs = [max(int(n).bit_length() - 1, 0) for n in ns]
+        nsa = (C.c_size_t * max(k, 1))(*[int(n) for n in ns])
+        pr, prp = _out_u64(k)
+        ev, evp = _out_u64(sum(2 * v for v in vs))
+        r, rp = _out_u64(sum(2 * v * (v - 1) for v in vs))
+        pt, ptp = _out_u64(sum(v * (v - 1) // 2 for v in vs))
+        lc, lcp = _out_u64(sum(vs))
+        lp, lpp = _out_u64(sum(vs))
+        le, lep = _out_u64(k)
+        cp = None
+        if challenges is not None:
+            c, cp = self._cat_u64(challenges)
+        bad = C.c_size_t(0)
+        self.check_batch(fn(self.h, k, ptrs, nsa, cp, prp, evp, rp, ptp, lcp, lpp, lep, C.byref(bad)), bad)
+        out, eo, ro, po, vo = [], 0, 0, 0, 0
+        for i, v in enumerate(vs):
+            out.append((int(pr[i]), ev[eo: eo + 2 * v].copy(), r[ro: ro + 2 * v * (v - 1)].copy(), pt[po: po + v * (v - 1) // 2].copy(),
+                        lc[vo: vo + v].copy(), lp[vo: vo + v].copy(), int(le[i])))
+            eo, ro, po, vo = eo + 2 * v, ro + 2 * v * (v - 1), po + v * (v - 1) // 2, vo + v
+        return out
+
+    def grand_product_prove_batch(self, tables, challenges=None):
+        """zigz_grand_product_prove_batch: for every column (2^v canonical words) the layered grand-product proof (product,
+        layer_evals [2 v], rounds [2 v (v - 1)], points [v (v - 1) / 2], layer_challenges [v], leaf_point [v], leaf_eval);
+        challenges[i] (optional, v (v + 1) / 2 words in order of use) fixes instance i's challenges (no transcript)."""
+        arrs = [_u64(t) for t in tables]
+        ptrs = (u64p * max(len(arrs), 1))(*[p for _, p in arrs])
+        return self._grand_product_prove(lib.zigz_grand_product_prove_batch, ptrs, [len(t) for t in tables], challenges)
+
+    def dev_grand_product_prove_batch(self, d_tables, ns, challenges=None):
+        """zigz_dev_grand_product_prove_batch over device-resident columns (packed u32 canonical, 16-byte aligned; only read)."""
+        ptrs = (vp * max(len(ns), 1))(*[int(d) for d in d_tables])
+        return self._grand_product_prove(lib.zigz_dev_grand_product_prove_batch, ptrs, ns, challenges)
+
+    def _grand_product_verify(self, fn, ptrs, ns, proofs, flags):
+        k = len(ns)
+        nsa = (C.c_size_t * max(k, 1))(*[int(n) for n in ns])
+        pr, prp = self._cat_u64([[int(p[0]) for p in proofs]])
+        ev, evp = self._cat_u64([p[1] for p in proofs])
+        r, rp = self._cat_u64([p[2] for p in proofs])
+        lp, lpp = self._cat_u64([p[5] for p in proofs])
+        le, lep = self._cat_u64([[int(p[6]) for p in proofs]])
+        verd, vdp = _out_u8(k)
+        exp, ep = _out_u64(k)
+        orc, op = _out_u64(k)
+        rej, bad = C.c_size_t(0), C.c_size_t(0)
+        self.check_batch(fn(self.h, k, ptrs, nsa, prp, evp, rp, lpp, lep, int(flags), vdp, ep, op, C.byref(rej), C.byref(bad)), bad)
+        deferred = bool(int(flags) & GRAND_PRODUCT_LEAF_DEFERRED)
+        return verd[:k].copy(), [int(x) for x in exp[:k]], [None if deferred else int(x) for x in orc[:k]], rej.value
+
+    def grand_product_verify_batch(self, tables, proofs, flags=0, ns=None):
+        """zigz_grand_product_verify_batch: proofs[i] as grand_product_prove_batch returns it (Fiat-Shamir), tables[i] the column.
+        flags = GRAND_PRODUCT_LEAF_DEFERRED: tables must be None and ns gives the lengths; the column's evaluation at the leaf
+        point is then the caller's check.  Returns (verdicts np.uint8, expected_evals, oracle_evals, n_rejected)."""
+        if tables is None:
+            return self._grand_product_verify(lib.zigz_grand_product_verify_batch, None, ns, proofs, flags)
+        arrs = [_u64(t) for t in tables]
+        ptrs = (u64p * max(len(arrs), 1))(*[p for _, p in arrs])
+        return self._grand_product_verify(lib.zigz_grand_product_verify_batch, ptrs, [len(t) for t in tables], proofs, flags)
+
+    def dev_grand_product_verify_batch(self, d_tables, ns, proofs, flags=0):
+        """zigz_dev_grand_product_verify_batch over device-resident columns (d_tables None with GRAND_PRODUCT_LEAF_DEFERRED)."""
+        ptrs = None if d_tables is None else (vp * max(len(ns), 1))(*[int(d) for d in d_tables])
+        return self._grand_product_verify(lib.zigz_dev_grand_product_verify_batch, ptrs, ns, proofs, flags)
 
     def _merkle_batch_out(self, rc, bad, k, roots, heights, handle, ns, keep):
         self.check_batch(rc, bad)
